@@ -8,15 +8,21 @@ are resident in HBM before the timed region.  value = envs * substeps * steps
 * n_gpus / max-over-ranks wall time.
 
   python bench.py [--gpus N --steps K --warmup W --substeps S --scenario robocup|lunar]
+                  [--dump-outputs DIR] [--full]
   torchrun --nproc-per-node N bench.py --gpus N ...   (one process per GPU, RCCL)
+
+A plain run does what the headline needs and nothing else: set up, warm up,
+time the K steps, print the line.  --dump-outputs DIR then writes what the
+last timed step computed (DIR/<name>.npy, see dump_outputs).  --full adds the
+CPU baselines and the secondary figures below.
 
 Rank r owns the envs with global ids [r*B, (r+1)*B) of the N*B-env run and
 builds them from those ids (RoboCupEnv(env_offset, total_envs)).  After each
 launch the observation tensor is all-gathered over RCCL (asynchronous, double
 buffered), the north star's one collective.
 
-The JSON line also carries, measured in the same process after the headline
-(rank 0, --extras auto):
+With --full the JSON line also carries, measured in the same process after the
+headline (rank 0; --extras off / --cpu-baseline off leave a part of them out):
   workload_stats  finite-env fraction and restarts per env-step of the headline
                   workload (the reference's RoboCup goes NaN at step 1)
   k1              the headline scene with ONE driver step per launch (the launch
@@ -70,9 +76,14 @@ def parse():
     ap.add_argument("--substeps", type=int, default=64)
     ap.add_argument("--envs", type=int, default=4096, help="envs per GPU")
     ap.add_argument("--scenario", default="robocup", choices=["robocup", "lunar", "box"])
-    ap.add_argument("--cpu-baseline", default="auto", choices=["auto", "off"])
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure the CPU baselines (--cpu-baseline) and the secondary "
+                         "figures (--extras); a plain run measures the headline alone")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy")
+    ap.add_argument("--cpu-baseline", default="auto", choices=["auto", "off"], help="with --full")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--extras", default="auto", choices=["auto", "off"])
+    ap.add_argument("--extras", default="auto", choices=["auto", "off"], help="with --full")
     ap.add_argument("--mode", default="step", choices=["step", "grad"])
     ap.add_argument("--dump-gather", default=None, help="save the last all-gathered and local observation (.npz)")
     ap.add_argument("--envs-per-wave", type=int, default=0, choices=[0, 1, 2, 4, 8],
@@ -95,6 +106,8 @@ def parse():
                     help="--mode grad: the RoboCup tape backward at two waves per env group (the library default, 1) "
                          "or one (0; other scenes always run one, DESIGN section 3); recorded in config")
     a = ap.parse_args()
+    if not a.full:  # a plain run: the headline alone
+        a.cpu_baseline = a.extras = "off"
     refuse_overrides()
     # the two-wave forms' library switches (read at the first launch)
     os.environ["COTIX_KEY_HELPER"] = str(a.key_helper)
@@ -163,6 +176,27 @@ def obs_checksum(obs):
     a = ((v * (i * 48271 % M)) % M).sum() % M
     b = ((v * (i * 69621 % M)) % M).sum() % M
     return a * M + b
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: what the last timed step handed its caller, one
+    <path>/<name>.npy per array, float32 as it is and every other type as
+    float64 (exact for the 32-bit integer keys, flags and counters).  All
+    files together stay under DUMP_MAX_BYTES: an array over its share is cut
+    to a fixed sample of its flattened elements (sorted indices drawn from
+    seed 0, the same for every run of the same shape)."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_MAX_BYTES // max(len(arrays), 1)
+    for name, t in arrays.items():
+        x = t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+        x = x if x.dtype == np.float32 else x.astype(np.float64)
+        if x.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(x.size, share // x.itemsize, replace=False))
+            x = x.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), x)
 
 
 def timed_launches(fn, steps, warmup, separate=False):
@@ -502,6 +536,7 @@ def main():
     obs_local = [torch.empty(B, nbody, 6, device=dev) for _ in range(2)] if dist else None
     pending = [None, None]
     launches = [0]
+    returned = {}  # what the last env.step handed back (--dump-outputs)
     evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(a.steps)]
 
     def one_step(i=None):
@@ -511,7 +546,7 @@ def main():
         if i is not None:
             evs[i][0].record()
         # the step kernel writes the observation straight into the send buffer
-        env.step(a.substeps, obs_out=obs_local[k] if dist is not None else None)
+        returned["obs"] = env.step(a.substeps, obs_out=obs_local[k] if dist is not None else None)
         if i is not None:
             evs[i][1].record()
         if dist is not None:  # north star: RCCL all-gather of the observation tensor
@@ -546,6 +581,11 @@ def main():
     if dist:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     wall = float(tmax.item())
+    if a.dump_outputs and rank == 0 and a.steps > 0:
+        # the step's return value (the observation) and the state it leaves in the
+        # env's tensors: bodies SoA, key chains, error flags, restart counters
+        dump_outputs(a.dump_outputs, {"obs": returned["obs"], "dyn": env.world.dyn, "keys": env.world.keys,
+                                      "err": env.world.err, "resets": env.resets})
     resets = int(env.resets.sum().item())
     gather = None
     if dist is not None:
@@ -708,7 +748,7 @@ def run_grad(pa, dev, B, T, steps, warmup, rank, world_size, dist=None, scenario
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     wall = float(tmax.item())
     ga = state["ga"]
-    return {"value": B * T * steps * world_size / wall, "wall": wall, "variant": variant,
+    return {"value": B * T * steps * world_size / wall, "wall": wall, "variant": variant, "ret": state["ret"], "ga": ga,
             "fwd_ms": sum(e0.elapsed_time(e1) for e0, e1 in evf) / steps,
             "bwd_ms": sum(e0.elapsed_time(e1) for e0, e1 in evb) / steps,
             "finite": float(torch.isfinite(ga).all(dim=2).all(dim=0).float().mean().item()),
@@ -748,6 +788,8 @@ def main_grad(a):
     r = run_grad(pa, dev, B, T, a.steps, a.warmup, rank, world_size, dist,
                  "box" if box else ("lunar" if lunar else "robocup"),
                  (a.envs_per_wave, a.specialize, a.bwd_envs_per_wave))
+    if a.dump_outputs and rank == 0:  # the rollout's return and its gradient w.r.t. the actions
+        dump_outputs(a.dump_outputs, {"ret": r["ret"], "grad_action": r["ga"]})
     nb = 7 if box else (4 if lunar else 5)
     key = "grad_box" if box else ("grad_lunar" if lunar else "grad")
     # algorithmic HBM bytes per env-step.  Backward: saved state (nb x 6 f32)

@@ -29,7 +29,8 @@ def test_bench_rccl_path_single_rank(tmp_path):
     env = dict(os.environ, WORLD_SIZE="1", RANK="0", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1",
                MASTER_PORT=str(_free_port()), COTIX_BENCH_FORCE_DIST="1")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1",
-                        "--substeps", "8", "--cpu-baseline", "off", "--extras", "off", "--dump-gather", dump],
+                        "--substeps", "8", "--cpu-baseline", "off", "--extras", "off", "--dump-gather", dump,
+                        "--dump-outputs", str(tmp_path / "outputs")],
                        env=env, cwd=ROOT, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
@@ -39,6 +40,15 @@ def test_bench_rccl_path_single_rank(tmp_path):
     # the gathered tensor == cotix_observe of the local state == the SoA state transposed
     assert np.array_equal(d["gathered"].view(np.uint32), d["local"].view(np.uint32))
     assert np.array_equal(d["local"].view(np.uint32), d["dyn"].transpose(2, 0, 1).view(np.uint32))
+    # --dump-outputs: the last timed step's return value and the state it left, f32 / f64 arrays
+    outs = {n: np.load(str(tmp_path / "outputs" / (n + ".npy"))) for n in ("obs", "dyn", "keys", "err", "resets")}
+    assert outs["obs"].dtype == np.float32 and outs["dyn"].dtype == np.float32
+    assert all(outs[n].dtype == np.float64 for n in ("keys", "err", "resets"))
+    assert np.array_equal(outs["obs"].view(np.uint32), d["local"].view(np.uint32))
+    assert np.array_equal(outs["dyn"].view(np.uint32), d["dyn"].view(np.uint32))
+    assert outs["keys"].shape == (4096, 2) and outs["err"].shape == outs["resets"].shape == (4096,)
+    assert set(line) >= {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"}
+    assert "cpu_baseline" not in line and "k1" not in line  # a run without --full: the headline alone
 
 
 def _reference_obs(B, substeps, launches):

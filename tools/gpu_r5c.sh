@@ -9,7 +9,7 @@ timeout -k 10 700 python -u -m pytest tests -m gpu -x -v -p no:cacheprovider --t
 rc=$?; echo "pytest rc=$rc"; tail -3 $O/pytest_gpu.log; [ $rc -eq 0 ] || exit $rc
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1
 rc=$?; echo "smoke rc=$rc"; [ $rc -eq 0 ] || { tail -20 $O/smoke.log; exit $rc; }
-timeout -k 10 400 python bench.py > $O/bench.json 2> $O/bench.err
+timeout -k 10 400 python bench.py --full > $O/bench.json 2> $O/bench.err
 rc=$?; echo "bench rc=$rc"; [ $rc -eq 0 ] || { tail $O/bench.err; exit $rc; }
 python tools/show_bench.py $O/bench.json 2>/dev/null || cut -c1-400 $O/bench.json
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/k1floor -o run --output-format csv -- python tools/k1_floor.py > $O/k1floor.out 2> $O/k1floor.err || { tail $O/k1floor.err; exit 1; }
