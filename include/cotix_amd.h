@@ -387,6 +387,34 @@ int cotix_rollout_backward_ex(cotix_scene* scene, const float* saved_dyn, const 
                               const uint32_t* tape, const float* geom, int geom_stride, int B, int n_steps, float dt,
                               int stages, const float* action, int action_body, const float* ret_weights,
                               float* grad_action, float* grad_dyn0, cotix_stream_t stream);
+/* cotix_rollout_backward_ex plus the gradient of the return with respect to
+ * the body parameters (every body leaf is differentiable in the reference,
+ * cotix/_bodies.py:140-154; they enter the step through resolve_collision /
+ * apply_impulse, cotix/_collision_resolution.py:52-146, and the LunarLander
+ * joints, cotix/_lunar_lander.py:176-212):
+ *   grad_params device f32 [n_bodies][4][B] (nullable), written (not
+ *        accumulated): word [b][k][g] = d ret[g] / d parameter k of body b,
+ *        summed over the rollout's steps; k in the order of the scene's
+ *        [n_bodies][4] parameter block: mass, inertia, elasticity,
+ *        friction_coefficient.  The layout is grad_dyn0's (structure of
+ *        arrays, the env index last).
+ * Semantics are jax.grad's through the executed branches: e = min(e1, e2)
+ * sends a tie's cotangent 1/2-1/2 to the two bodies; a static body (mass =
+ * inf) gets exact zeros where its cotangent is finite and NaN where the
+ * adjoint chain already carries NaN.
+ * Shared-parameter scenes: every env reads the scene's one parameter block,
+ * so [b][k][g] is env g's derivative with respect to the shared value; the
+ * gradient of a batch objective is the caller's sum over g.
+ * COTIX_SCENE_PER_ENV_BODY_PARAMS scenes: [b][k][g] is the derivative with
+ * respect to env g's own word of its geometry row; geom and a non-zero
+ * geom_stride are then required.
+ * With grad_params == NULL this is cotix_rollout_backward_ex (the same
+ * kernels, the same bits); with it, grad_action and grad_dyn0 keep their bits
+ * and the tape backward runs at one wave per env group. */
+int cotix_rollout_backward_ex2(cotix_scene* scene, const float* saved_dyn, const uint32_t* saved_keys,
+                               const uint32_t* tape, const float* geom, int geom_stride, int B, int n_steps, float dt,
+                               int stages, const float* action, int action_body, const float* ret_weights,
+                               float* grad_action, float* grad_dyn0, float* grad_params, cotix_stream_t stream);
 
 /* Body-level operators (UniversalShape, cotix/_universal_shape.py:87-132), per env:
  * cotix_body_penetration: collides_with (GJK over every part pair of the two

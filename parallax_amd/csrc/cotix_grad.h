@@ -12,8 +12,21 @@
 // so branch decisions are those the forward step took.
 //
 // Shape gradients use the geometry layout of the forward path: circle
-// (r, cx, cy, pad) and AABB (lo.x, lo.y, up.x, up.y); the radius, masses,
-// inertias, elasticities and frictions are constants (not differentiated).
+// (r, cx, cy, pad) and AABB (lo.x, lo.y, up.x, up.y); the radius is a
+// constant (not differentiated).
+//
+// Body parameters (mass, inertia, elasticity, friction_coefficient -- every
+// body leaf is differentiable in the reference, cotix/_bodies.py:140-154) are
+// differentiated on request: resolve_vjp<true> / fixed_vjp<true> also return
+// the cotangents of the two bodies' parameters (GP, a compile-time flag: the
+// <false> instantiations are the code without them).  The parameters enter
+// the step only through apply_impulse (v += imp / m, w += torque / I), the
+// resolution's denominator (1/m1 + 1/m2 + lev1/I1 + lev2/I2), e = min(e1, e2)
+// and mu = (mu1 + mu2) / 2 (cotix/_collision_resolution.py:52-146) and the
+// LunarLander joints' impulses (cotix/_lunar_lander.py:176-212).  Quotients
+// are differentiated as -g * ((a / b) / b) and reciprocals as -g * (1/b)^2, so
+// a static body (mass = inf) gets an exact zero from a finite cotangent and
+// NaN from a NaN one, as autograd of the same expressions does.
 #pragma once
 #include "cotix_device.h"
 
@@ -382,8 +395,20 @@ CX_DEV void convex_contact_vjp_edge(const Shape& A, const Shape& B, v2 e0, v2 e1
 CX_DEV float drot_dot(v2 g, v2 v, float s, float c) {
   return g.x * (-s * v.x - c * v.y) + g.y * (c * v.x - s * v.y);
 }
+// apply_impulse(b, imp, point) (cotix/_collision_resolution.py:68-73):
+// v += imp / m, w += crs(r, imp) / I -> the cotangents of m and I from the
+// cotangent g of the body after the impulse; for the pair (b1, i1), (b2, i2)
+CX_DEV void impulse_par_vjp(const Dyn& g1, const Params& m1, v2 r1, v2 i1, const Dyn& g2, const Params& m2, v2 r2, v2 i2,
+                            float* gm1, float* gI1, float* gm2, float* gI2) {
+  *gm1 += -(g1.vx * ((i1.x / m1.mass) / m1.mass)) + -(g1.vy * ((i1.y / m1.mass) / m1.mass));
+  *gI1 += -(g1.w * ((crs(r1, i1) / m1.inertia) / m1.inertia));
+  *gm2 += -(g2.vx * ((i2.x / m2.mass) / m2.mass)) + -(g2.vy * ((i2.y / m2.mass) / m2.mass));
+  *gI2 += -(g2.w * ((crs(r2, i2) / m2.inertia) / m2.inertia));
+}
+// GP: gq[0..3] += the cotangents of (m1, I1, m2, I2)
+template <bool GP = false>
 CX_DEV void fixed_vjp(const Dyn& b1, const Params& m1, v2 c1, const Dyn& b2, const Params& m2, v2 c2, Dyn& g1, Dyn& g2,
-                      v2& gc1, v2& gc2) {
+                      v2& gc1, v2& gc2, float* gq = nullptr) {
   const float f05 = 0.05f;
   const v2 r1 = sub(c1, v2{b1.px, b1.py}), r2 = sub(c2, v2{b2.px, b2.py});
   const v2 dp = sub(c1, c2);
@@ -391,6 +416,7 @@ CX_DEV void fixed_vjp(const Dyn& b1, const Params& m1, v2 c1, const Dyn& b2, con
   const float nd = nrm(dv), k = nd + 0.1f;
   const v2 imp = v2{dp.x * 1.0f + (dv.x * k) * f05, dp.y * 1.0f + (dv.y * k) * f05};
   // apply_impulse(b1, -imp, c1), apply_impulse(b2, imp, c2)
+  if (GP) impulse_par_vjp(g1, m1, r1, neg(imp), g2, m2, r2, imp, &gq[0], &gq[1], &gq[2], &gq[3]);
   v2 gimp = v2{-g1.vx / m1.mass + g2.vx / m2.mass, -g1.vy / m1.mass + g2.vy / m2.mass};
   const float gt1 = g1.w / m1.inertia, gt2 = g2.w / m2.inertia;
   v2 gr1 = scl(v2{-imp.y, imp.x}, gt1), gr2 = scl(v2{imp.y, -imp.x}, gt2);  // torque = crs(r, -+imp)
@@ -427,8 +453,11 @@ CX_DEV void fixed_vjp(const Dyn& b1, const Params& m1, v2 c1, const Dyn& b2, con
 // branch that applies the impulses.  In: the pre-resolution bodies, the
 // cotangents g1/g2 of the post-resolution bodies.  Out: g1/g2 become the
 // cotangents of the pre-resolution bodies; gpen/gcp those of the contact.
+// GP: gq[0..7] = the cotangents of body 1's and body 2's (mass, inertia,
+// elasticity, friction_coefficient) from this resolution
+template <bool GP = false>
 CX_DEV void resolve_vjp(const Dyn& b1, const Params& m1, const Dyn& b2, const Params& m2, v2 pen, v2 cp, Dyn& g1,
-                        Dyn& g2, v2& gpen, v2& gcp, Baum bm = baum_default()) {
+                        Dyn& g2, v2& gpen, v2& gcp, Baum bm = baum_default(), float* gq = nullptr) {
   // forward values (cotix_device.h resolve_collision)
   const v2 r1 = sub(cp, v2{b1.px, b1.py}), r2 = sub(cp, v2{b2.px, b2.py});
   const v2 v1 = velocity_at(b1, cp), v2_ = velocity_at(b2, cp);
@@ -451,6 +480,11 @@ CX_DEV void resolve_vjp(const Dyn& b1, const Params& m1, const Dyn& b2, const Pa
   const v2 imp = add(scl(n, ni), scl(vdu, idr));
 
   // apply_impulse(b1, -imp, cp); apply_impulse(b2, imp, cp)  (:68-73)
+  if (GP) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) gq[k] = 0.0f;
+    impulse_par_vjp(g1, m1, r1, neg(imp), g2, m2, r2, imp, &gq[0], &gq[1], &gq[4], &gq[5]);
+  }
   v2 gimp = v2{-g1.vx / m1.mass + g2.vx / m2.mass, -g1.vy / m1.mass + g2.vy / m2.mass};
   v2 gr1 = v2{0.0f, 0.0f}, gr2 = v2{0.0f, 0.0f};
   {
@@ -470,6 +504,11 @@ CX_DEV void resolve_vjp(const Dyn& b1, const Params& m1, const Dyn& b2, const Pa
   float gidr0 = 0.0f, glo = 0.0f, ghi = 0.0f;
   vjp_clip(idr0, 0.0f, ni * mu, gidr, &gidr0, &glo, &ghi);
   gni += ghi * mu;
+  if (GP) {  // mu = (mu1 + mu2) / 2
+    const float gmu = (ghi * ni) / 2.0f;
+    gq[3] += gmu;
+    gq[7] += gmu;
+  }
   // idr0 = -vdn / den
   float gvdn = -gidr0 / den;
   float gden = gidr0 * vdn / (den * den);
@@ -486,6 +525,15 @@ CX_DEV void resolve_vjp(const Dyn& b1, const Params& m1, const Dyn& b2, const Pa
   gden += -gni * nim / (den * den);
   gr1 = add(gr1, scl(r1, 2.0f * (gden / m1.inertia)));
   gr2 = add(gr2, scl(r2, 2.0f * (gden / m2.inertia)));
+  if (GP) {
+    const float q1 = 1.0f / m1.mass, q2 = 1.0f / m2.mass;
+    gq[0] += -(gden * (q1 * q1));
+    gq[4] += -(gden * (q2 * q2));
+    gq[1] += -(gden * ((lev1 / m1.inertia) / m1.inertia));
+    gq[5] += -(gden * ((lev2 / m2.inertia) / m2.inertia));
+    // e = min(e1, e2) (ties 1/2-1/2), nim = -(1 + e) * vn - ...
+    vjp_min(m1.elast, m2.elast, -(gnim * vn), &gq[2], &gq[6]);
+  }
   // nim = -(1 + e) * vn - k * |pen| / dt
   gvn += -(1.0f + e) * gnim;
   float gpn = -(bm.k / bm.dt) * gnim;

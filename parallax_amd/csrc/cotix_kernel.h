@@ -258,6 +258,10 @@ struct KArgs {
   int nfe_len;             // env-steps per NFE (WFE_scale); n_steps is a multiple of it (judge on)
   JudgeArgs judge;         // device AbstractJudge (judge.on == 0: off)
   CtlArgs ctl;             // device AbstractControl (ctl.on == 0: off)
+  // backward: [nb][4][B] d ret / d (mass, inertia, elasticity, friction_coefficient)
+  // of every body, summed over the steps, or null (cotix_rollout_backward_ex2;
+  // the GP programs below)
+  float* grad_params;
 };
 
 // The rollout's saved rows (save_dyn: nb*6 state words per env-step; tape:
@@ -3484,8 +3488,35 @@ CX_DEV void part_pose_vjp(const Ctx& c, Tile<EW> t, int p, int e, const cx::Shap
 }
 // the joints of LunarLander.step in reverse (cotix_grad.h fixed_vjp): the
 // tile holds the post-collider, pre-joint bodies (the re-play skips them)
+// the body parameters' gradient (KArgs::grad_params), GP programs only.  Env
+// g's words belong to the lane that runs its reverse chain (phase G: lane e of
+// the wave) from the zeroing to the last step: plain read-modify-writes in
+// program order, no atomics, no tile words.  Every form adds the same terms
+// in the same order (step T-1 .. 0; the joints, then the resolutions nb-1 ..
+// 0, body i's words then body j's): the same bits.
+CX_DEV void gpar_add(const KArgs& a, int g, int b, int k, float v) {
+  float* p = a.grad_params + (size_t)(4 * b + k) * (size_t)a.B + (size_t)g;
+  *p = *p + v;
+}
 template <int EW>
-CX_DEV void joints_vjp(const Ctx& c, Tile<EW> t, int e) {
+CX_DEV void gpar_zero(const KArgs& a, const Ctx& c, int env0, int lane) {
+  for (int e = lane; e < EW; e += WAVE) {
+    const int g = env0 + e;
+    if (g >= a.B) continue;
+    for (int w = 0; w < 4 * c.nb; ++w) a.grad_params[(size_t)w * (size_t)a.B + (size_t)g] = 0.0f;
+  }
+}
+// a resolution's parameter cotangents (resolve_vjp<true>'s gq) of bodies i, j
+CX_DEV void gpar_resolution(const KArgs& a, int g, int i, int j, const float (&gq)[8]) {
+#pragma unroll
+  for (int k = 0; k < 4; ++k) gpar_add(a, g, i, k, gq[k]);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) gpar_add(a, g, j, k, gq[4 + k]);
+}
+// GP: the masses' and inertias' cotangents of the lander and both legs, summed
+// over the four impulse pairs (in the reverse order), into env g's grad_params
+template <int EW, bool GP = false>
+CX_DEV void joints_vjp(const Ctx& c, Tile<EW> t, int e, const KArgs* a = nullptr, int g_env = 0) {
   using namespace cx;
   const Lay& L = c.L;
   Dyn d[3], g[3];
@@ -3543,11 +3574,26 @@ CX_DEV void joints_vjp(const Ctx& c, Tile<EW> t, int e) {
   g[1].w = g[1].w * 0.95f;
   g[2].w = g[2].w * 0.95f;
   v2 gc1[4], gc2[4];
+  float gmI[3][2] = {{0.0f, 0.0f}, {0.0f, 0.0f}, {0.0f, 0.0f}};  // (GP) d / d (mass, inertia) of the three bodies
 #pragma unroll
   for (int f = 3; f >= 0; --f) {
     gc1[f] = v2{0.0f, 0.0f};
     gc2[f] = v2{0.0f, 0.0f};
-    fixed_vjp(pre1[f], m[0], c1[f], pre2[f], m[leg[f]], c2[f], g[0], g[leg[f]], gc1[f], gc2[f]);
+    float gq[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    fixed_vjp<GP>(pre1[f], m[0], c1[f], pre2[f], m[leg[f]], c2[f], g[0], g[leg[f]], gc1[f], gc2[f], gq);
+    if (GP) {
+      gmI[0][0] += gq[0];
+      gmI[0][1] += gq[1];
+      gmI[leg[f]][0] += gq[2];
+      gmI[leg[f]][1] += gq[3];
+    }
+  }
+  if (GP) {
+#pragma unroll
+    for (int b = 0; b < 3; ++b) {
+      gpar_add(*a, g_env, b, 0, gmI[b][0]);
+      gpar_add(*a, g_env, b, 1, gmI[b][1]);
+    }
   }
 #pragma unroll
   for (int f = 0; f < 4; ++f) {  // anchors: rotate(local, angle) + position
@@ -3635,7 +3681,8 @@ CX_DEV void ph_GE(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, int lane) 
 // TILE: the adjoints are read from and written to the tile's adj words inside
 // the chain's own loops (g_regs: the one-wave form's schedule, the adjoints
 // live only across one step); otherwise the caller's registers carry them
-template <int EW, int NB, bool TILE = false>
+// GP: the body parameters' gradient too (gpar_resolution)
+template <int EW, int NB, bool TILE = false, bool GP = false>
 CX_DEV void g_chain(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, int e, int step, float (&g)[NB][6],
                     GradOut* go = nullptr) {
   using namespace cx;
@@ -3676,8 +3723,11 @@ CX_DEV void g_chain(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, int e, i
       const Dyn bj = Dyn{pxj, pyj, t.f(ro + 4, e), t.f(ro + 5, e), anj, t.f(ro + 6, e)};
       Dyn gi = Dyn{g[i][0], g[i][1], g[i][2], g[i][3], g[i][4], g[i][5]};
       v2 gpen = v2{0.0f, 0.0f}, gcp = v2{0.0f, 0.0f};
-      resolve_vjp(bi, body_par<EW>(c, t, i, e), bj, body_par<EW>(c, t, j, e),
-                  v2{t.f(co, e), t.f(co + 1, e)}, v2{t.f(co + 2, e), t.f(co + 3, e)}, gi, gj, gpen, gcp, baum_of(sc));
+      float gq[8];
+      resolve_vjp<GP>(bi, body_par<EW>(c, t, i, e), bj, body_par<EW>(c, t, j, e),
+                      v2{t.f(co, e), t.f(co + 1, e)}, v2{t.f(co + 2, e), t.f(co + 3, e)}, gi, gj, gpen, gcp, baum_of(sc),
+                      gq);
+      if (GP) gpar_resolution(a, env0 + e, i, j, gq);
       const int pa = t.ti(sc.o_cpa + cid), pb = t.ti(sc.o_cpb + cid), fn = t.ti(sc.o_cfn + cid);
       const int ka = t.ti(sc.o_pkind + pa), kb = t.ti(sc.o_pkind + pb);
       const int wa = L.world + t.ti(sc.o_pwoff + pa), wb = L.world + t.ti(sc.o_pwoff + pb);
@@ -3744,13 +3794,13 @@ CX_DEV void g_chain(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, int e, i
       for (int k = 0; k < 6; ++k) t.f(L.adj + 6 * b + k, e) = g[b][k];
   }
 }
-template <int EW, int NB>
+template <int EW, int NB, bool GP = false>
 CX_DEV void g_regs(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, int e, int step, GradOut* go = nullptr) {
   float g[NB][6];
-  g_chain<EW, NB, true>(a, c, t, env0, e, step, g, go);
+  g_chain<EW, NB, true, GP>(a, c, t, env0, e, step, g, go);
 }
 
-template <int EW, int FNSET = FNS_ANALYTIC>
+template <int EW, int FNSET = FNS_ANALYTIC, bool GP = false>
 CX_DEV void ph_G(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, int lane, int step, GradOut* go = nullptr) {
   using namespace cx;
   const SceneHdr& sc = c.sh;
@@ -3761,15 +3811,15 @@ CX_DEV void ph_G(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, int lane, i
     if (g >= a.B) continue;
 #ifndef COTIX_NO_GREGS  // (tooling: the tile form for every scene, tests/test_grad_cpu.py checks the two agree)
     if (FNSET == FNS_ANALYTIC && nb == 5) {  // RoboCup
-      g_regs<EW, 5>(a, c, t, env0, e, step, go);
+      g_regs<EW, 5, GP>(a, c, t, env0, e, step, go);
       continue;
     }
     if (FNSET == FNS_ANALYTIC && nb == 7) {  // the box world
-      g_regs<EW, 7>(a, c, t, env0, e, step, go);
+      g_regs<EW, 7, GP>(a, c, t, env0, e, step, go);
       continue;
     }
 #endif
-    if (FNSET != FNS_ANALYTIC && (a.stages & COTIX_STAGE_LUNAR) && nb >= 3) joints_vjp<EW>(c, t, e);
+    if (FNSET != FNS_ANALYTIC && (a.stages & COTIX_STAGE_LUNAR) && nb >= 3) joints_vjp<EW, GP>(c, t, e, &a, g);
     if (a.stages & COTIX_STAGE_COLLIDER) {
       for (int i = nb - 1; i >= 0; --i) {  // resolutions in reverse order
         const int ro = L.rec + REC_W * i;
@@ -3783,9 +3833,11 @@ CX_DEV void ph_G(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, int lane, i
         Dyn gi = Dyn{t.f(ai, e), t.f(ai + 1, e), t.f(ai + 2, e), t.f(ai + 3, e), t.f(ai + 4, e), t.f(ai + 5, e)};
         Dyn gj = Dyn{t.f(aj, e), t.f(aj + 1, e), t.f(aj + 2, e), t.f(aj + 3, e), t.f(aj + 4, e), t.f(aj + 5, e)};
         v2 gpen = v2{0.0f, 0.0f}, gcp = v2{0.0f, 0.0f};
-        resolve_vjp(bi, body_par<EW>(c, t, i, e), bj, body_par<EW>(c, t, j, e),
-                    v2{t.f(co, e), t.f(co + 1, e)}, v2{t.f(co + 2, e), t.f(co + 3, e)}, gi, gj, gpen, gcp,
-                    baum_of(sc));
+        float gq[8];
+        resolve_vjp<GP>(bi, body_par<EW>(c, t, i, e), bj, body_par<EW>(c, t, j, e),
+                        v2{t.f(co, e), t.f(co + 1, e)}, v2{t.f(co + 2, e), t.f(co + 3, e)}, gi, gj, gpen, gcp,
+                        baum_of(sc), gq);
+        if (GP) gpar_resolution(a, g, i, j, gq);
         // the contact: fn(world(part pa), world(part pb)); world = local + body position
         const int pa = t.ti(sc.o_cpa + cid), pb = t.ti(sc.o_cpb + cid), fn = t.ti(sc.o_cfn + cid);
         const int ka = t.ti(sc.o_pkind + pa), kb = t.ti(sc.o_pkind + pb);
@@ -4256,9 +4308,11 @@ CX_DEV void run_wave(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, const R
 // (recording the pre-resolution velocities), GE and G as in the re-play.
 // No key split, narrowphase, RNG scan or choice runs: the tape holds their
 // outcome, and every value the VJPs read is bit-identical to the re-play's
-template <int EW, int FNSET, class R>
+// GP: with the body parameters' gradient (KArgs::grad_params, zeroed here)
+template <int EW, int FNSET, bool GP = false, class R>
 CX_DEV void run_wave_backward_tape(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, const R& run) {
   run(PH_ADJ, [&](int l) {
+    if (GP) gpar_zero<EW>(a, c, env0, l);
     ws_poly_init<EW>(c, t, l);
     ph_geo<EW>(a, c, t, env0, l);
     ph_adj_init<EW>(a, c, t, env0, l);
@@ -4293,7 +4347,7 @@ CX_DEV void run_wave_backward_tape(const KArgs& a, const Ctx& c, Tile<EW> t, int
       else
         run(PH_GE, [&](int l) { ph_GE<EW>(a, c, t, env0, l); });
     }
-    run(PH_G, [&](int l) { ph_G<EW, FNSET>(a, c, t, env0, l, step, &go); });
+    run(PH_G, [&](int l) { ph_G<EW, FNSET, GP>(a, c, t, env0, l, step, &go); });
   };
   if (TR && rows_restore<EW>(a, c)) {  // rows, two steps ahead (two register sets: the loop unrolled by two)
     struct Pre {
@@ -4479,9 +4533,11 @@ CX_DEV void run_backward_split(const KArgs& a, const Ctx& c, Tile<EW> t0, Tile<E
 
 // backward: steps n_steps-1 .. 0, each re-played from the saved state (so
 // every discrete choice is the forward's) and then reversed by phase G
-template <int EW, int FNSET, class R>
+// GP: with the body parameters' gradient (KArgs::grad_params, zeroed here)
+template <int EW, int FNSET, bool GP = false, class R>
 CX_DEV void run_wave_backward(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, const R& run) {
   run(PH_ADJ, [&](int l) {
+    if (GP) gpar_zero<EW>(a, c, env0, l);
     ws_poly_init<EW>(c, t, l);
     ph_geo<EW>(a, c, t, env0, l);
     ph_adj_init<EW>(a, c, t, env0, l);
@@ -4503,7 +4559,7 @@ CX_DEV void run_wave_backward(const KArgs& a, const Ctx& c, Tile<EW> t, int env0
     run(PH_E, [&](int l) { ph_E<EW, true>(a, c, t, env0, l, c.L.sk0); });
     if (FNSET != FNS_ANALYTIC && (a.stages & COTIX_STAGE_COLLIDER) && ge_fits(c))
       run(PH_GE, [&](int l) { ph_GE<EW>(a, c, t, env0, l); });
-    run(PH_G, [&](int l) { ph_G<EW, FNSET>(a, c, t, env0, l, step); });
+    run(PH_G, [&](int l) { ph_G<EW, FNSET, GP>(a, c, t, env0, l, step); });
   }
   run(PH_ADJ, [&](int l) { ph_adj_store<EW>(a, c, t, env0, l); });
 }

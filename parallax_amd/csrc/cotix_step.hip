@@ -435,8 +435,10 @@ static int launch(cotix_scene* scene, const cxk::KArgs& ka0, int mode, cotix_str
   // tiles always fit WPB to a workgroup)
   const int spec = wpb == cxl::WPB ? scene_spec(scene) : cxk::SPEC_GENERIC;
   // the tape backward at two waves per env group where the scene allows it
-  // and two tiles per group fit (cxk::run_backward_split; the same bits)
-  if (mode == 4 && EW == 4 && wpb == cxl::WPB && split_bwd_enabled() &&
+  // and two tiles per group fit (cxk::run_backward_split; the same bits).
+  // A launch that asks for the body parameters' gradient runs the one-wave
+  // MODE 4 (the consumer chain does not carry them)
+  if (mode == 4 && EW == 4 && wpb == cxl::WPB && split_bwd_enabled() && ka.grad_params == nullptr &&
       cxk::launch_fnset(fs, mode) == cxk::FNS_ANALYTIC &&
       cxk::split_bwd_ok<4>(ka, cxk::make_ctx<4>(scene->host)) &&
       scene_lds_w(scene, 4, 2 * cxl::WPB) <= LDS_CAP) {
@@ -610,6 +612,14 @@ int cotix_rollout_backward_ex(cotix_scene* scene, const float* saved_dyn, const 
                               const uint32_t* tape, const float* geom, int geom_stride, int B, int n_steps, float dt,
                               int stages, const float* action, int action_body, const float* ret_weights,
                               float* grad_action, float* grad_dyn0, cotix_stream_t stream) {
+  return cotix_rollout_backward_ex2(scene, saved_dyn, saved_keys, tape, geom, geom_stride, B, n_steps, dt, stages,
+                                    action, action_body, ret_weights, grad_action, grad_dyn0, nullptr, stream);
+}
+
+int cotix_rollout_backward_ex2(cotix_scene* scene, const float* saved_dyn, const uint32_t* saved_keys,
+                               const uint32_t* tape, const float* geom, int geom_stride, int B, int n_steps, float dt,
+                               int stages, const float* action, int action_body, const float* ret_weights,
+                               float* grad_action, float* grad_dyn0, float* grad_params, cotix_stream_t stream) {
   if (check_step_args(scene, saved_dyn, saved_keys, geom, geom_stride, B, n_steps, stages, action, action_body))
     return -1;
   if (!ret_weights) return fail("null argument");
@@ -619,6 +629,9 @@ int cotix_rollout_backward_ex(cotix_scene* scene, const float* saved_dyn, const 
                 std::to_string(cx::CP_GJK_MAX));
   if ((stages & COTIX_STAGE_LUNAR) && !(scene->fnset & ~FNS_ANALYTIC))
     return fail("differentiable rollout: the LunarLander joint stage needs the polygon program (a polygon scene)");
+  // a per-env scene reads every env's parameters from its own geometry row
+  if (grad_params && scene->host.epar != 0 && (!geom || geom_stride == 0))
+    return fail("grad_params of a per-env-parameter scene needs geom with a geom_stride (one row per env)");
   if (B == 0 || n_steps == 0) return 0;
   cxk::KArgs ka{};
   ka.dyn = nullptr;
@@ -640,6 +653,7 @@ int cotix_rollout_backward_ex(cotix_scene* scene, const float* saved_dyn, const 
   ka.tw = cxk::tape_words(scene->host.nb, scene->host.nc, scene->host.poly);
   ka.grad_action = grad_action;
   ka.grad_dyn = grad_dyn0;
+  ka.grad_params = grad_params;
   for (int k = 0; k < scene->host.nb * 6; ++k) ka.ret_w[k] = ret_weights[k];
   return launch(scene, ka, tape ? 4 : 2, stream);
 }

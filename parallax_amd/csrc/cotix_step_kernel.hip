@@ -83,8 +83,11 @@ struct WaveRun {
 // MODE 0: step, 1: rollout forward (saves + return, + tape), 2: rollout
 // backward re-playing the forward, 3: eval with the device judge / control
 // (cotix_eval), 4: rollout backward from the forward's tape;
-// SPEC: scene specialization (cxk::SPEC_*, compile-time dimensions)
-template <int EW, int FNSET, int MODE, int SPEC = cxk::SPEC_GENERIC>
+// SPEC: scene specialization (cxk::SPEC_*, compile-time dimensions);
+// GP (MODE 2 and 4): the backward with the body parameters' gradient
+// (KArgs::grad_params) -- instantiations of their own, so a launch that does
+// not ask for it runs the kernels it ran before
+template <int EW, int FNSET, int MODE, int SPEC = cxk::SPEC_GENERIC, bool GP = false>
 __global__ __launch_bounds__(WPB * 64) void step_kernel(cxk::KArgs a) {
   extern __shared__ uint32_t lds[];
   CXK_STAMP(st0);
@@ -141,9 +144,9 @@ __global__ __launch_bounds__(WPB * 64) void step_kernel(cxk::KArgs a) {
   const WaveRun run{lane};
 #endif
   if (MODE == 4)
-    cxk::run_wave_backward_tape<EW, FNSET>(a, c, t, env0, run);
+    cxk::run_wave_backward_tape<EW, FNSET, GP>(a, c, t, env0, run);
   else if (MODE == 2)
-    cxk::run_wave_backward<EW, FNSET>(a, c, t, env0, run);
+    cxk::run_wave_backward<EW, FNSET, GP>(a, c, t, env0, run);
   else if (MODE == 3)
     cxk::run_wave<EW, FNSET, false, true>(a, c, t, env0, run, true);
   else
@@ -324,6 +327,31 @@ hipError_t cxl::CXL_NAME(COTIX_EW)(const cxk::KArgs& ka, int fs, int mode, size_
   constexpr int F_AN = FNS_ANALYTIC, F_PP = FNS_ANALYTIC | FNS_CONVEX, F_AP = F_PP | cxk::FNS_AABB_POLY,
                 F_ALL = F_AP | FNS_CIRCLE_POLY;
   const int F = cxk::launch_fnset(fs, mode);  // the contact-function program for this scene
+  // the backward with the body parameters' gradient: the generic one-wave
+  // programs, and the tape backward of RoboCup's and the box world's
+  // specializations at the default tiling
+  if (ka.grad_params != nullptr) {
+    if (mode != 2 && mode != 4) return hipErrorInvalidValue;
+#define COTIX_LAUNCH_GP(FS, BW, SP) \
+  hipLaunchKernelGGL((step_kernel<EW, FS, BW, SP, true>), grid, block, lds, st, ka)
+#if COTIX_EW == 4
+    if (mode == 4 && F == F_AN && spec == cxk::SPEC_ROBOCUP)
+      COTIX_LAUNCH_GP(F_AN, 4, cxk::SPEC_ROBOCUP);
+    else if (mode == 4 && F == F_AN && spec == cxk::SPEC_BOX)
+      COTIX_LAUNCH_GP(F_AN, 4, cxk::SPEC_BOX);
+    else
+#endif
+    if (mode == 4 && F == F_AN)
+      COTIX_LAUNCH_GP(F_AN, 4, cxk::SPEC_GENERIC);
+    else if (mode == 4)
+      COTIX_LAUNCH_GP(F_ALL, 4, cxk::SPEC_GENERIC);
+    else if (F == F_AN)
+      COTIX_LAUNCH_GP(F_AN, 2, cxk::SPEC_GENERIC);
+    else
+      COTIX_LAUNCH_GP(F_ALL, 2, cxk::SPEC_GENERIC);
+#undef COTIX_LAUNCH_GP
+    return hipGetLastError();
+  }
 #if COTIX_EW == 4 || COTIX_EW == 2
   // the reference-scene specializations: every program of RoboCup at the
   // default tiling, the step programs (mode 0) at 4 and 2 envs per wave

@@ -18,6 +18,12 @@ ties for max/min/clip.  Circle, AABB and polygon contacts (GJK/EPA through
 EPA's final edge and contact_from_edges), circle x polygon contacts (through
 every GJK / EPA point the circle's direction-dependent support builds) and
 the LunarLander joints (stages=_ffi.STAGES_LUNAR).
+
+Body parameters: rollout_backward(want_params=True) also returns d ret /
+d (mass, inertia, elasticity, friction_coefficient) of every body and env
+(cotix_rollout_backward_ex2), and rollout(body_params=...) makes them a
+torch.autograd input -- every body leaf is differentiable in the reference
+(cotix/_bodies.py:140-154).
 """
 import numpy as np
 import torch
@@ -94,15 +100,27 @@ def trajectory(saved, B):
     return sd.permute(0, 2, 1, 3).reshape(T, nd // 6, 6, nblk * 4)[..., :B].contiguous()
 
 
-def rollout_backward(world, saved, want_dyn0=False, replay=False):
+def rollout_backward(world, saved, want_dyn0=False, replay=False, want_params=False):
     """d ret / d actions [T, B, 2] (and d ret / d initial state [nb, 6, B]):
     from the forward's tape, or (replay=True, or no tape saved) re-playing
-    the forward's steps."""
+    the forward's steps.  want_params: returns (ga, gd, gp) with gp f32
+    [nb, 4, B] = d ret[env] / d (mass, inertia, elasticity,
+    friction_coefficient) of every body, summed over the steps; on a
+    shared-parameter world every env's derivative with respect to the shared
+    value (sum over envs for a batch objective)."""
     nb, B = len(world.bodies), world.B
     T = saved["actions"].shape[0]
     ga = torch.empty(T, B, 2, device=world.device, dtype=torch.float32)
     gd = torch.empty(nb, 6, B, device=world.device, dtype=torch.float32) if want_dyn0 else None
     tp = None if replay else saved.get("tape")
+    if want_params:
+        gp = torch.empty(nb, 4, B, device=world.device, dtype=torch.float32)
+        _ffi.check(_ffi.lib.cotix_rollout_backward_ex2(
+            world.scene.handle, _ffi.ptr(saved["dyn"]), _ffi.ptr(saved["keys"]), _ffi.ptr(tp), _ffi.ptr(world.geom),
+            world.geom_stride, B, T, saved["dt"], saved["stages"], _ffi.ptr(saved["actions"]), saved["action_body"],
+            saved["w"].ctypes.data_as(_ffi._P), _ffi.ptr(ga), _ffi.ptr(gd), _ffi.ptr(gp),
+            _ffi.stream_ptr(world.device)), "cotix_rollout_backward_ex2")
+        return ga, gd, gp
     _ffi.check(_ffi.lib.cotix_rollout_backward_ex(
         world.scene.handle, _ffi.ptr(saved["dyn"]), _ffi.ptr(saved["keys"]), _ffi.ptr(tp), _ffi.ptr(world.geom),
         world.geom_stride, B, T, saved["dt"], saved["stages"], _ffi.ptr(saved["actions"]), saved["action_body"],
@@ -124,7 +142,58 @@ class _Rollout(torch.autograd.Function):
         return ga * g_ret.to(ga.dtype)[None, :, None], None, None, None, None, None
 
 
-def rollout(world, actions, action_body=None, ret_weights=None, dt=1e-2, stages=_ffi.STAGES_ROBOCUP):
+class _RolloutParams(torch.autograd.Function):
+    """The rollout with the body parameters as a second differentiable input."""
+
+    @staticmethod
+    def forward(ctx, actions, body_params, world, action_body, ret_weights, dt, stages):
+        per_env = world.scene.per_env_params
+        if per_env:  # the parameter words of every env's geometry row (the backward reads them again)
+            world.body_params().copy_(body_params.detach())
+        ret, saved = rollout_forward(world, actions.detach(), action_body, ret_weights, dt, stages)
+        ctx.world, ctx.saved, ctx.per_env = world, saved, per_env
+        ctx.geom_version = world.geom._version
+        return ret
+
+    @staticmethod
+    def backward(ctx, g_ret):
+        if ctx.world.geom._version != ctx.geom_version:
+            raise RuntimeError("the world's geometry / body parameters changed between rollout() and backward()")
+        want_p = ctx.needs_input_grad[1]
+        out = rollout_backward(ctx.world, ctx.saved, want_params=want_p)
+        g = g_ret.to(out[0].dtype)
+        ga = out[0] * g[None, :, None]
+        gp = None
+        if want_p:
+            gp = out[2] * g[None, None, :]  # [nb, 4, B]
+            gp = gp.permute(2, 0, 1).contiguous() if ctx.per_env else gp.sum(dim=2)
+        return ga, gp, None, None, None, None, None
+
+
+def rollout(world, actions, action_body=None, ret_weights=None, dt=1e-2, stages=_ffi.STAGES_ROBOCUP,
+            body_params=None):
     """R[env] (differentiable w.r.t. actions via torch.autograd); advances
-    `world` by T steps in place."""
-    return _Rollout.apply(actions, world, action_body, ret_weights, dt, stages)
+    `world` by T steps in place.
+
+    body_params: also differentiable w.r.t. the bodies' (mass, inertia,
+    elasticity, friction_coefficient).  On a per-env-parameter world a
+    [B, n_bodies, 4] tensor, copied into the world's parameter words
+    (World.body_params()) before the forward; its gradient is d ret / d params
+    weighted by the incoming cotangent, as the actions' is.  On a
+    shared-parameter world a [n_bodies, 4] tensor that equals the scene's
+    parameters bit for bit (they are compiled into the scene at creation:
+    ValueError otherwise); its gradient is the sum over the envs."""
+    if body_params is None:
+        return _Rollout.apply(actions, world, action_body, ret_weights, dt, stages)
+    have = world.body_params()
+    if tuple(body_params.shape) != tuple(have.shape):
+        raise ValueError("body_params must be %s for this world, got %s" % (tuple(have.shape),
+                                                                             tuple(body_params.shape)))
+    if body_params.dtype != torch.float32 or body_params.device != have.device:
+        raise ValueError("body_params must be a float32 tensor on the world's device")
+    if not world.scene.per_env_params and not torch.equal(body_params.detach().view(torch.int32),
+                                                          have.view(torch.int32)):
+        raise ValueError("body_params of a shared-parameter world must equal the scene's parameters bit for bit "
+                         "(World.body_params(): they are compiled into the scene at creation); build the world "
+                         "with per-env parameters to vary them")
+    return _RolloutParams.apply(actions, body_params, world, action_body, ret_weights, dt, stages)

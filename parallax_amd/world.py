@@ -35,6 +35,7 @@ class Scene:
         # env's geometry row (include/cotix_amd.h COTIX_SCENE_PER_ENV_BODY_PARAMS)
         self.per_env_params = any(b.params_per_env() for b in bodies)
         params = torch.tensor([b.template_params() for b in bodies], dtype=torch.float32)
+        self.body_params = params  # [n_bodies, 4]: the constants the scene compiles (the template of a per-env scene)
         part_body, part_type, part_nv = [], [], []
         for i, b in enumerate(bodies):
             for p in b.shape.parts:
@@ -195,6 +196,17 @@ class World:
 
     def set_dyn(self, dyn):
         self.dyn.copy_(dyn)
+
+    def body_params(self):
+        """The bodies' (mass, inertia, elasticity, friction_coefficient) as the
+        kernel reads them: [B, n_bodies, 4] for a per-env scene -- a view of the
+        last 4 * n_bodies words of each geometry row, so writes reach the next
+        launch -- or [n_bodies, 4] for a shared one (a copy of the constants
+        compiled into the scene at creation)."""
+        nb = len(self.bodies)
+        if self.scene.per_env_params:
+            return self.geom[:, self.geom.shape[1] - 4 * nb:].view(self.B, nb, 4)
+        return self.scene.body_params.to(self.device)
 
     # -- hot path ---------------------------------------------------------
     def step(self, n_steps=1, dt=1e-2, stages=_ffi.STAGES_ROBOCUP, action=None, action_body=0,
