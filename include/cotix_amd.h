@@ -193,6 +193,13 @@ int cotix_scene_info(const cotix_scene* scene, int* n_contacts, int* n_cells, in
 int cotix_scene_set_variant(cotix_scene* scene, int envs_per_wave, int specialize);
 int cotix_scene_variant(const cotix_scene* scene, int* envs_per_wave, int* spec);
 int cotix_scene_waves_per_group(const cotix_scene* scene);
+/* The kernel form of the scene's last step launch (cotix_step*): 0 the step
+ * kernel at one wave per env group, 1 with a key-window helper wave per env
+ * group (launches of more than 16 steps of the RoboCup specialization), 2
+ * the helper also computing the collider scan's first-level keys (where the
+ * ring fits the LDS without costing the launch residency).  Every form
+ * computes the same bits; set by the launch, for tests and measurements. */
+int cotix_scene_last_step_form(cotix_scene* scene);
 
 /* Fused step, n_steps times, in place.
  *   dyn   device f32 [n_bodies][6][B]  (px, py, vx, vy, angle, angular_velocity)

@@ -79,6 +79,7 @@ SIGNATURES = {
     "cotix_gjk_ex": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "cotix_scene_create_ex2": (_I, [_I, _P, _I, _P, _P, _P, _P, _I, ctypes.POINTER(_P)]),
     "cotix_scene_waves_per_group": (_I, [_P]),
+    "cotix_scene_last_step_form": (_I, [_P]),
     "cotix_epa": (_I, [_I, _P, _P, _P, _I, _P, _P]),
     "cotix_threefry2x32": (_I, [_P, _P, _P, _I, _P]),
     "cotix_random_split": (_I, [_P, _I, _I, _P, _P]),
@@ -95,6 +96,11 @@ SIGNATURES = {
 }
 
 
+# entry points an older build given as COTIX_AMD_LIB (bench.py --lib, A/B
+# measurements against a parent commit) may lack; this tree's build has them
+OPTIONAL = {"cotix_scene_last_step_form"}
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(
@@ -102,6 +108,8 @@ def _load():
             "(hipcc --offload-arch=gfx950); there is no CPU fallback" % LIB_PATH)
     lib = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in SIGNATURES.items():
+        if name in OPTIONAL and not hasattr(lib, name):
+            continue
         fn = getattr(lib, name)
         fn.restype = res
         fn.argtypes = args

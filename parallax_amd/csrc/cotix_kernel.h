@@ -670,7 +670,7 @@ template <int EW>
 CX_DEV void k_one_regs(const KArgs& a, const Ctx& c, Tile<EW> t, int lane, uint32_t k0, uint32_t k1);
 // the key chain of a one-step launch runs in the prologue, on the keys in
 // registers, while the batch of state reads is in flight (ph_load)
-CX_DEV bool keys_on(const KArgs& a) {
+CX_HD bool keys_on(const KArgs& a) {
   return (a.stages & (COTIX_STAGE_COLLIDER | COTIX_STAGE_ADVANCE_KEY)) != 0 && !CXK_SKIP(a, 16);
 }
 CX_DEV bool k_in_prologue(const KArgs& a) { return keys_on(a) && a.n_steps == 1; }
@@ -2305,8 +2305,12 @@ CX_DEV bool m0_active(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, int id
 // a drawer's candidate: its item's next candidate word (slot word: the item's
 // scan base | end << 12 | id << 25), 0xFFFFFFFF past the item's list; pass:
 // the candidate's bernoulli draw passed and its contact is not NaN
-template <int EW>
-CX_DEV uint32_t m_draw(const Ctx& c, Tile<EW> t, uint32_t sw, int q, int kso, bool& pass) {
+// L1: the first-level key split(skey_t, N2)[i2] comes from the step's slot of
+// the level-1 key ring (key_l1_fill, the helper wave's; kl1: the slot's first
+// word in the tile's addressing, ko1: the first type's N2, where the second
+// type's keys start -- run_wave's) -- two LDS reads in place of two blocks
+template <int EW, bool L1 = false>
+CX_DEV uint32_t m_draw(const Ctx& c, Tile<EW> t, uint32_t sw, int q, int kso, bool& pass, int kl1 = 0, int ko1 = 0) {
   using namespace cx;
   const SceneHdr& sc = c.sh;
   pass = false;
@@ -2316,10 +2320,16 @@ CX_DEV uint32_t m_draw(const Ctx& c, Tile<EW> t, uint32_t sw, int q, int kso, bo
   const uint32_t cd = t.tb[sc.o_cand + idx];
   const int i1 = cd & 511u, i2 = (cd >> 9) & 511u, cid = (cd >> 18) & 511u, ty = cd >> 27;
   const float cpx = t.f(c.L.con + 4 * cid + 2, e), cpy = t.f(c.L.con + 4 * cid + 3, e);
-  const key2 sk = key2{t.w(kso + 2 + 2 * ty, e), t.w(kso + 3 + 2 * ty, e)};
+  int ko = i2;  // L1: the key's index in the ring slot -- the earlier types' N2, then i2
+  if constexpr (L1) {
+    ko += ty > 0 ? ko1 : 0;
+    for (int p = 1; p + 1 < c.nt; ++p) ko += p < ty ? t.ti(sc.o_tn2 + p) : 0;  // (a third type on: the tables)
+  }
+  const key2 sk = L1 ? key2{t.w(kl1 + 2 * ko, e), t.w(kl1 + 2 * ko + 1, e)}
+                     : key2{t.w(kso + 2 + 2 * ty, e), t.w(kso + 3 + 2 * ty, e)};
   const bool part = sc.prng != 0;
   const bool valid = !(isn(cpx) || isn(cpy));  // a NaN candidate never writes
-  const key2 k2 = split_at_l(sk, (uint32_t)t.ti(sc.o_tn2 + ty), (uint32_t)i2, part);  // :264
+  const key2 k2 = L1 ? sk : split_at_l(sk, (uint32_t)t.ti(sc.o_tn2 + ty), (uint32_t)i2, part);  // :264
   const key2 k = split_at_l(k2, (uint32_t)t.ti(sc.o_tn1 + ty), (uint32_t)i1, part);   // :254
   pass = bernoulli_l(split_at_l(k, 2u, 0u, part), sc.pc, part) & valid;              // :222-223
   CXK_STAT(draws, 1);
@@ -2386,8 +2396,9 @@ CX_DEV bool m_settle(Tile<EW> t, MItem& it, bool drew, uint64_t bits, uint32_t w
   it.pos += G;
   return it.cb + it.pos < it.ce;
 }
-template <int EW>
-CX_DEV void ph_M_fused(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, int lane, int kso, const MConst& mc) {
+template <int EW, bool L1 = false>
+CX_DEV void ph_M_fused(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, int lane, int kso, const MConst& mc,
+                       int kl1 = 0, int ko1 = 0) {
   const bool two = c.nl * EW > WAVE;  // uniform (a constant in the specialized kernels)
   MItem it0 = mc.it[0], it1 = mc.it[1];
   const bool f0 = m0_active_c<EW>(a, c, t, env0, lane, mc.cm[0]);
@@ -2436,7 +2447,7 @@ CX_DEV void ph_M_fused(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, int l
     const int slot = rank_of_lane(lane, G), q = lane - slot * G;
     bool pass = false;
     uint32_t cd = 0xFFFFFFFFu;
-    if (slot < ns) cd = m_draw<EW>(c, t, t.ws[WS_FLAG + slot], q, kso, pass);
+    if (slot < ns) cd = m_draw<EW, L1>(c, t, t.ws[WS_FLAG + slot], q, kso, pass, kl1, ko1);
     const uint64_t pm = ballot(pass);
     // an owner's item: the first passing draw among its drawers r*G .. r*G+G-1
     const uint64_t gm = G == WAVE ? ~0ull : ((1ull << G) - 1ull);
@@ -4012,9 +4023,11 @@ CX_DEV void transform_phases(const KArgs& a, const Ctx& c, Tile<EW> t, int env0,
   }
 }
 // TAPE: the rollout forward with a tape (phase B records EPA's edges)
-template <int EW, int FNSET, bool PRE, class R, bool AB = false, bool TAPE = false>
+// L1: the fused scan reads its first-level keys from the level-1 key ring
+// (kl1: this step's slot, m_draw)
+template <int EW, int FNSET, bool PRE, class R, bool AB = false, bool TAPE = false, bool L1 = false>
 CX_DEV void collider_phases(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, const R& run, int slot, int kso,
-                            const MConst& mc, int step = 0) {
+                            const MConst& mc, int step = 0, int kl1 = 0, int ko1 = 0) {
   if (!AB && !CXK_SKIP(a, 1)) transform_phases<EW, FNSET>(a, c, t, env0, run);
   if ((FNSET & FNS_CONVEX) != 0 && c.sh.poly && (a.stages & COTIX_STAGE_BROADPHASE) && !CXK_SKIP(a, 2)) {
     run(PH_BP0, [&](int l) { ph_BP0<EW>(a, c, t, env0, l); });
@@ -4044,7 +4057,7 @@ CX_DEV void collider_phases(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, 
     }
   }
   if (!CXK_SKIP(a, 4) && c.nl > 0 && scan_fused<EW>(c)) {
-    run(PH_C1, [&](int l) { ph_M_fused<EW>(a, c, t, env0, l, kso, mc); });
+    run(PH_C1, [&](int l) { ph_M_fused<EW, L1>(a, c, t, env0, l, kso, mc, kl1, ko1); });
   } else if (!CXK_SKIP(a, 4) && c.nl > 0) {
     for (int ch = 0; ch * WAVE < c.nl * EW; ++ch) {
       run(PH_C0, [&](int l) { ph_C0<EW>(a, c, t, env0, l, ch); });
@@ -4161,6 +4174,139 @@ CX_HD size_t help_lds_bytes(const SceneHdr& s, int wpb) {
   return 4 * ((size_t)s.nhot + (size_t)wpb * (help_region_words<EW>(c) + KWIN * c.L.kww * EW));
 }
 
+// ---------------------------------------------------------------------------
+// The level-1 key ring (the key helper's second job).  The collider scan's
+// draw derives its key in three splits, and the first, split(skey_t, N2)[i2],
+// depends on the step's type key only: tn2[0] + .. + tn2[nt - 1] keys per
+// env-step (RoboCup: 22 + 8), never on the physics.  The helper wave computes
+// them KL1R steps at a time into an LDS ring of two halves, laid out
+// [step in ring][key][word][env] in the tile's addressing, and the scan
+// reads two words per draw in place of running two blocks (m_draw's L1).
+// The step wave waits at one workgroup barrier per half: before the scan of
+// every KL1R-th step, step 0 included (the helper fills the first half while
+// the step wave runs window 0's K0-K2 and phases A / T / B) -- at the start
+// of the step where it is a later window's first, the key window's barrier,
+// which then releases both.  The helper passes the same barriers:
+//   for s0 = 0, KL1R, ..:  [s0 a window start > 0: the window]
+//                          the half of steps s0 .. s0 + KL1R - 1, barrier
+// It writes half h after the barrier that released half h ^ 1, when the step
+// wave has left the steps that read h; a window's buffer likewise.  Window
+// 0's type keys, which the step wave computes for itself while the helper
+// already needs them, the helper derives into its own buffer (the odd
+// windows': free until window 1 is due, after the second half).
+// A help policy takes part by declaring `static constexpr bool l1 = true` and
+// `int l1o`, the ring's first word from the tile's in tile words.
+// ---------------------------------------------------------------------------
+constexpr int KL1R = 8;  // steps per ring half
+static_assert(KWIN % KL1R == 0, "a key window is whole ring halves (key_l1_next's barrier order)");
+template <class H, class = void>
+struct help_l1 {
+  static constexpr bool value = false;
+};
+template <class H>
+struct help_l1<H, decltype((void)H::l1)> {
+  static constexpr bool value = H::l1;
+};
+template <class H>
+CX_MF int help_l1o(const H& h) {
+  if constexpr (help_l1<H>::value)
+    return h.l1o;
+  else
+    return 0;
+}
+// the keys of one env-step's ring slot, from the scene's tables
+CX_HD int key_l1_keys(const SceneHdr& s, const uint32_t* tb) {
+  int n = 0;
+  for (int q = 0; q < s.nt; ++q) n += (int)tb[s.o_tn2 + q];
+  return n;
+}
+// the ring's words per env group (two halves) and the workgroup's LDS bytes
+// of the helper form with it (nk1: key_l1_keys)
+template <int EW>
+CX_HD int key_l1_ring_words(int nk1) { return 2 * KL1R * 2 * nk1 * EW; }
+template <int EW>
+CX_HD size_t help_l1_lds_bytes(const SceneHdr& s, int wpb, int nk1) {
+  return help_lds_bytes<EW>(s, wpb) + 4 * (size_t)wpb * key_l1_ring_words<EW>(nk1);
+}
+// the barriers of a launch in this form: one per ring half, a window's with
+// its first half's (step waves, helper waves and idle waves all pass this many)
+CX_HD int key_l1_barriers(const KArgs& a) {
+  return keys_on(a) && a.n_steps > 0 ? (a.n_steps + KL1R - 1) / KL1R : 0;
+}
+template <int EW>
+struct KeyL1 {
+  KeyHelper<EW> kh;
+  int l1o = 0;     // the ring's first word from kh.tm's, in tile words
+  int nk1 = 0;     // keys per env-step
+  int s0 = 0;      // the next half's first step
+  int q = 0;       // barriers reached
+};
+// the ring half of steps s0 .. s0 + n - 1 from the type keys of their window
+// (tk: the buffer that holds it).  Items (key block, env), a step at a time.
+// Legacy layout: block j of split(skey_t, N) gives flat words j and N + j
+// (cx::split_word's block for either), so the whole split is N blocks;
+// partitionable: key i is one block (cx::split_at_l).
+template <int EW>
+CX_DEV void key_l1_fill(const Ctx& c, Tile<EW> tr, Tile<EW> tk, int l1o, int nk1, int s0, int n, int lane) {
+  using namespace cx;
+  const SceneHdr& sc = c.sh;
+  const bool part = sc.prng != 0;
+#ifdef COTIX_EMU_POISON
+  // test instrumentation: the half's previous keys die here (a short last
+  // half leaves poison, not the keys of 2 KL1R steps ago)
+  for (int w = lane; w < KL1R * 2 * nk1 * EW; w += WAVE)
+    tr.u[(l1o + (s0 % (2 * KL1R)) * 2 * nk1) * EW + w] = 0x7FBADBADu;
+  lockstep();
+#endif
+  for (int s = s0; s < s0 + n; ++s) {
+    const int ko = c.L.kw + (s % KWIN) * c.L.kww, ro = l1o + (s % (2 * KL1R)) * 2 * nk1;
+    for (int w = lane; w < nk1 * EW; w += WAVE) {
+      const int e = w % EW;
+      int j = w / EW, ty = 0, off = 0;  // block j of type ty, whose keys start at off
+      for (int p = 0; p + 1 < c.nt; ++p) {
+        const int np = tk.ti(sc.o_tn2 + p);
+        if (ty == p && j >= np) {
+          j -= np;
+          off += np;
+          ty = p + 1;
+        }
+      }
+      const uint32_t N = (uint32_t)tk.ti(sc.o_tn2 + ty);
+      const key2 sk = key2{tk.w(ko + 2 + 2 * ty, e), tk.w(ko + 3 + 2 * ty, e)};
+      if (part) {
+        const key2 k = split_at_l(sk, N, (uint32_t)j, true);
+        tr.w(ro + 2 * (off + j), e) = k.a;
+        tr.w(ro + 2 * (off + j) + 1, e) = k.b;
+      } else {
+        // split_word's block for flat words m = j (its y0) and m = N + j (its y1)
+        const key2 r = threefry(sk, (uint32_t)j, N + (uint32_t)j);
+        tr.w(ro + 2 * off + j, e) = r.a;
+        tr.w(ro + 2 * off + (int)N + j, e) = r.b;
+      }
+    }
+  }
+}
+// the helper's work up to its next barrier (the caller passes it after each
+// call): key_l1_barriers(a) calls in a launch
+template <int EW, class R>
+CX_DEV void key_l1_next(const KArgs& a, const Ctx& c, KeyL1<EW>& h, const R& run) {
+  KeyHelper<EW>& kh = h.kh;
+  if (h.q++ == 0) {  // the launch key, then window 0's chain and type keys into the helper's own buffer
+    const int n0 = a.n_steps < KWIN ? a.n_steps : KWIN;
+    run(PH_K, [&](int l) {
+      const int e = l >> 1, g = kh.env0 + e;
+      if (l < 2 * EW && g < a.B) kh.k = cx::key2{a.keys[2 * (size_t)g], a.keys[2 * (size_t)g + 1]};
+      k0_regs<EW>(a, c, kh.th, l, n0, kh.k, true);
+    });
+    run(PH_K, [&](int l) { ph_K1<EW>(c, kh.th, l, n0); });
+  }
+  if (h.s0 > 0 && h.s0 % KWIN == 0) key_helper_next<EW>(a, c, kh, run);  // window s0 / KWIN, then its first half
+  const int w = h.s0 / KWIN, n = a.n_steps - h.s0 < KL1R ? a.n_steps - h.s0 : KL1R;
+  const Tile<EW> tk = (w == 0 || (w & 1)) ? kh.th : kh.tm;
+  run(PH_K, [&](int l) { key_l1_fill<EW>(c, kh.tm, tk, h.l1o, h.nk1, h.s0, n, l); });
+  h.s0 += KL1R;
+}
+
 template <int EW, int FNSET, bool ROLL, bool EVAL = false, bool SDEFER = false, class R = void, class H = NoKeyHelp>
 CX_DEV void run_wave(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, const R& run, bool loaded = false,
                      const H& help = H{}) {
@@ -4168,6 +4314,10 @@ CX_DEV void run_wave(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, const R
   static_assert(!(H::on && (ROLL || EVAL)), "the key helper runs the step program only");
   if (!loaded) run(PH_LOAD, [&](int l) { ph_load_fwd<EW, ROLL, EVAL>(a, c, t, env0, l); });
   const bool keys = keys_on(a);
+  // the level-1 key ring (a help policy's `l1`): the keys of a step's slot
+  constexpr bool L1 = help_l1<H>::value;
+  static_assert(!L1 || H::on, "the level-1 key ring is the key helper's");
+  const int nk1 = L1 ? key_l1_keys(c.sh, t.tb) : 0, ko1 = L1 && c.nt > 0 ? t.ti(c.sh.o_tn2) : 0;
   if (EVAL && a.judge.on) {  // the first NFE's start
     run(PH_J, [&](int l) { ph_JB<EW>(a, c, t, env0, l); });
     run(PH_J, [&](int l) { ph_JS<EW>(c, t, l); });
@@ -4238,6 +4388,10 @@ CX_DEV void run_wave(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, const R
     }
     // this step's sk0, skt in the key window (with a helper: odd windows in its buffer)
     const int kso = c.L.kw + (H::on && ((step / KWIN) & 1) ? help.kwalt : 0) + slot * c.L.kww;
+    // this step's slot of the level-1 key ring, and the barrier of its half
+    // (key_l1_next), passed before the step's scan
+    const int kl1 = L1 ? help_l1o(help) + (step % (2 * KL1R)) * 2 * nk1 : 0;
+    const bool l1bar = L1 && keys && step % KL1R == 0 && !(slot == 0 && step > 0);  // (else the window's)
     // phases A, T, B as one (circle / AABB scenes whose contact items fit the
     // phase's ABQ prefetched chunks; uniform)
     if (bconst) {  // phase A, then B from the launch-constant item words (no phase T)
@@ -4245,10 +4399,10 @@ CX_DEV void run_wave(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, const R
         act_next(l, step);
         ph_A<EW, true, EVAL, true>(a, c, t, env0, l, step, slot, apf, ac);
       });
-      if (a.stages & COTIX_STAGE_COLLIDER) {
-        run(PH_B, [&](int l) { ph_B_const<EW>(a, c, t, env0, l, bc); });
-        collider_phases<EW, FNSET, true, R, true, ROLL>(a, c, t, env0, run, slot, kso, mc, step);
-      }
+      if (a.stages & COTIX_STAGE_COLLIDER) run(PH_B, [&](int l) { ph_B_const<EW>(a, c, t, env0, l, bc); });
+      if (l1bar) help.bar();
+      if (a.stages & COTIX_STAGE_COLLIDER)
+        collider_phases<EW, FNSET, true, R, true, ROLL, L1>(a, c, t, env0, run, slot, kso, mc, step, kl1, ko1);
     } else if (FNSET == FNS_ANALYTIC && c.nc * EW <= ABQ * WAVE) {
       // stage 1 reads the pre-Euler state: every read is issued before phase
       // A's writes (stage 2); stage 3 computes the contacts
@@ -4259,15 +4413,17 @@ CX_DEV void run_wave(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, const R
             ph_A<EW, true, EVAL, SDEFER>(a, c, t, env0, l, step, slot, apf, ac);
           },
           [&](int l, const ABRegs& r) { ab_contacts<EW>(a, c, t, env0, l, r); });
-      if (a.stages & COTIX_STAGE_COLLIDER) collider_phases<EW, FNSET, true, R, FNSET == FNS_ANALYTIC, ROLL>(
-          a, c, t, env0, run, slot, kso, mc, step);
+      if (l1bar) help.bar();
+      if (a.stages & COTIX_STAGE_COLLIDER) collider_phases<EW, FNSET, true, R, FNSET == FNS_ANALYTIC, ROLL, L1>(
+          a, c, t, env0, run, slot, kso, mc, step, kl1, ko1);
     } else {
       run(PH_A, [&](int l) {
         act_next(l, step);
         ph_A<EW, true, EVAL, true>(a, c, t, env0, l, step, slot, apf, ac);
       });
+      if (l1bar) help.bar();
       if (a.stages & COTIX_STAGE_COLLIDER)
-        collider_phases<EW, FNSET, true, R, false, ROLL>(a, c, t, env0, run, slot, kso, mc, step);
+        collider_phases<EW, FNSET, true, R, false, ROLL, L1>(a, c, t, env0, run, slot, kso, mc, step, kl1, ko1);
     }
     if (a.trace_chosen != nullptr || a.trace_cells != nullptr)
       run(PH_TRACE, [&](int l) { ph_trace<EW>(a, c, t, env0, l, step); });

@@ -29,6 +29,8 @@ int launch_bwd_split(const cxk::KArgs& ka, int spec, size_t lds, hipStream_t st)
 // the step program (mode 0) with a key-window helper wave per env group
 // (EW = 4, RoboCup's specialization; cxk::KeyHelper), workgroups of 2 * WPB
 // waves with `lds` = cxk::help_lds_bytes<4>(header, WPB): 0 launched, 1 not
-// compiled for this scene (the caller launches step_kernel)
-int launch_step_help(const cxk::KArgs& ka, int spec, size_t lds, hipStream_t st);
+// compiled for this scene (the caller launches step_kernel).  l1: the helper
+// also fills the level-1 key ring (cxk::KeyL1), `lds` =
+// cxk::help_l1_lds_bytes<4>(header, WPB, cxk::key_l1_keys(header, tables))
+int launch_step_help(const cxk::KArgs& ka, int spec, size_t lds, hipStream_t st, bool l1 = false);
 }  // namespace cxl

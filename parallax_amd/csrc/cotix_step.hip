@@ -5,6 +5,7 @@
 // and in DESIGN.md).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <climits>
 #include <cstdio>
 #include <cstdlib>
@@ -46,6 +47,8 @@ struct cotix_scene {
   // the largest tiling whose LDS fits, lds_default_ew)
   int envs_per_wave = 4;
   int specialize = 1;
+  // the form of the last step launch (cotix_scene_last_step_form)
+  int last_step_form = 0;
 };
 // a workgroup's LDS at `ew` envs per wave and `wpb` waves (cxk::lds_bytes:
 // the hot tables + wpb tiles and wave scratches) and the hardware's 160 KiB
@@ -344,6 +347,11 @@ int cotix_scene_set_variant(cotix_scene* scene, int envs_per_wave, int specializ
   return 0;
 }
 
+int cotix_scene_last_step_form(cotix_scene* scene) {
+  if (!scene) return fail("null scene");
+  return scene->last_step_form;
+}
+
 int cotix_scene_waves_per_group(const cotix_scene* scene) {
   if (!scene) return fail("null scene");
   return scene_wpb(scene, scene->envs_per_wave);
@@ -411,6 +419,17 @@ static bool key_helper_enabled() {
   }();
   return on != 0;
 }
+// the device's compute units (the helper forms' residency arithmetic)
+static int device_cus() {
+  static const int n = [] {
+    int dev = 0, v = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+      return 0;
+    return v;
+  }();
+  return n;
+}
 // launch the fused step kernel (mode 0 step, 1 rollout forward, 2 backward re-play, 3 eval with a judge/control)
 static int launch(cotix_scene* scene, const cxk::KArgs& ka0, int mode, cotix_stream_t stream) {
   if (scene_upload(scene)) return -1;
@@ -450,9 +469,27 @@ static int launch(cotix_scene* scene, const cxk::KArgs& ka0, int mode, cotix_str
   if (mode == 0 && EW == 4 && wpb == cxl::WPB && ka.n_steps > cxk::KWIN && key_helper_enabled() &&
       cxk::launch_fnset(fs, mode) == cxk::FNS_ANALYTIC &&
       cxk::help_lds_bytes<4>(scene->host, cxl::WPB) <= LDS_CAP) {
-    const int r = cxl::launch_step_help(ka, spec, cxk::help_lds_bytes<4>(scene->host, cxl::WPB), st);
-    if (r == 0) return hip_check(hipGetLastError(), "step_help_kernel launch");
+    // with the level-1 key ring (cxk::KeyL1) where the scan is the fused one
+    // that reads it, the ring fits, and its LDS costs the launch no residency:
+    // a CU holds two of these workgroups by its registers (__launch_bounds__
+    // of 512 threads) and LDS_CAP / lds by its LDS, and the launch needs no
+    // more than its workgroups over the CUs
+    const size_t lds0 = cxk::help_lds_bytes<4>(scene->host, cxl::WPB);
+    const size_t lds1 =
+        cxk::help_l1_lds_bytes<4>(scene->host, cxl::WPB, cxk::key_l1_keys(scene->host, scene->host.hot));
+    const cxk::Ctx c4 = cxk::make_ctx<4>(scene->host);
+    const int cus = device_cus(), wgs = (ka.B + 4 * cxl::WPB - 1) / (4 * cxl::WPB);
+    const int need = cus > 0 ? (wgs + cus - 1) / cus : 2;
+    const int res0 = std::min<int>(2, (int)(LDS_CAP / lds0)), res1 = std::min<int>(2, (int)(LDS_CAP / lds1));
+    const bool l1 = (ka.stages & COTIX_STAGE_COLLIDER) && c4.nl > 0 && cxk::scan_fused<4>(c4) && lds1 <= LDS_CAP &&
+                    res1 >= std::min(res0, need);
+    const int r = cxl::launch_step_help(ka, spec, l1 ? lds1 : lds0, st, l1);
+    if (r == 0) {
+      scene->last_step_form = l1 ? 2 : 1;
+      return hip_check(hipGetLastError(), "step_help_kernel launch");
+    }
   }
+  if (mode == 0) scene->last_step_form = 0;
   hipError_t e;
 #ifdef COTIX_EW4_ONLY  // tooling builds (phase profile, ISA markers): the default tiling only
   e = cxl::launch_step_ew4(ka, fs, mode, lds, st, spec, wpb);

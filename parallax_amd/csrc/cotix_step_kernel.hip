@@ -228,7 +228,16 @@ struct GpuKeyHelp {
   int kwalt;
   __device__ __forceinline__ void bar() const { lds_barrier(); }
 };
-template <int FNSET, int SPEC, bool SDEFER>
+// L1: the helper also fills the level-1 key ring (cxk::KeyL1): WPB rings
+// follow the window buffers, and the workgroup passes cxk::key_l1_barriers
+struct GpuKeyHelpL1 {
+  static constexpr bool on = true;
+  static constexpr bool l1 = true;
+  int kwalt;
+  int l1o;
+  __device__ __forceinline__ void bar() const { lds_barrier(); }
+};
+template <int FNSET, int SPEC, bool SDEFER, bool L1 = false>
 __global__ __launch_bounds__(2 * WPB * 64) void step_help_kernel(cxk::KArgs a) {
   constexpr int EW = 4;
   extern __shared__ uint32_t lds[];
@@ -261,12 +270,34 @@ __global__ __launch_bounds__(2 * WPB * 64) void step_help_kernel(cxk::KArgs a) {
   if (stepper && env0 < a.B) cxk::ph_load_fwd<EW, false>(a, c, tm, env0, lane);
   __syncthreads();
   const WaveRun run{lane};
-  const int nbar = cxk::keys_on(a) ? cxk::key_helper_windows(a) : 0;
+  const int nbar = L1 ? cxk::key_l1_barriers(a) : cxk::keys_on(a) ? cxk::key_helper_windows(a) : 0;
   if (env0 >= a.B) {  // an idle wave keeps the barrier count
     for (int q = 0; q < nbar; ++q) lds_barrier();
     return;
   }
-  if (stepper) {
+  if constexpr (L1) {
+    const int nk1 = cxk::key_l1_keys(sh, lds);
+    const int l1o = (int)(lds + nhot + WPB * (rw + hw) + grp * cxk::key_l1_ring_words<EW>(nk1) - um) / EW;
+    if (stepper) {
+      // the step wave's instructions issue ahead of its helper's on their
+      // SIMD: the launch is the step waves' dependent chain (measured: 701.7
+      // -> 706.8 M env-steps/s, profiles/key_l1_ab_*.json)
+      __builtin_amdgcn_s_setprio(2);
+      const GpuKeyHelpL1 help{(int)(hb - um) / EW - c.L.kw, l1o};
+      cxk::run_wave<EW, FNSET, false, false, SDEFER>(a, c, tm, env0, run, true, help);
+    } else {
+      cxk::KeyL1<EW> h;
+      h.kh.tm = tm;
+      h.kh.th = cxk::Tile<EW>{hb - c.L.kw * EW, lds, nullptr};
+      h.kh.env0 = env0;
+      h.l1o = l1o;
+      h.nk1 = nk1;
+      for (int q = 0; q < nbar; ++q) {
+        cxk::key_l1_next<EW>(a, c, h, run);
+        lds_barrier();
+      }
+    }
+  } else if (stepper) {
     const GpuKeyHelp help{(int)(hb - um) / EW - c.L.kw};
     cxk::run_wave<EW, FNSET, false, false, SDEFER>(a, c, tm, env0, run, true, help);
   } else {
@@ -287,9 +318,11 @@ __global__ __launch_bounds__(2 * WPB * 64) void step_help_kernel(cxk::KArgs a) {
 
 #if COTIX_EW == 4
 // 0: launched; 1: not compiled for this scene / launch (the caller launches step_kernel)
-int cxl::launch_step_help(const cxk::KArgs& ka, int spec, size_t lds, hipStream_t st) {
+int cxl::launch_step_help(const cxk::KArgs& ka, int spec, size_t lds, hipStream_t st, bool l1) {
   const dim3 grid((ka.B + WPB * 4 - 1) / (WPB * 4)), block(2 * WPB * 64);
-  if (spec == cxk::SPEC_ROBOCUP)
+  if (spec == cxk::SPEC_ROBOCUP && l1)
+    hipLaunchKernelGGL((step_help_kernel<FNS_ANALYTIC, cxk::SPEC_ROBOCUP, true, true>), grid, block, lds, st, ka);
+  else if (spec == cxk::SPEC_ROBOCUP)
     hipLaunchKernelGGL((step_help_kernel<FNS_ANALYTIC, cxk::SPEC_ROBOCUP, true>), grid, block, lds, st, ka);
   else
     return 1;
