@@ -178,7 +178,9 @@ int cotix_scene_info(const cotix_scene* scene, int* n_contacts, int* n_cells, in
  * cotix_scene_variant reports what a step launch uses: the tiling and the
  * specialization id (0 generic, 1 RoboCup, 2 LunarLander, 3 RoboCup and 4
  * LunarLander in the partitionable PRNG layout, 5 the box world's structure:
- * 3 AABB walls and 4 circles, legacy layout).
+ * 3 AABB walls and 4 circles, legacy layout) of the step launch's plan -- the
+ * scene's specialization where the kernel list has its step program for the
+ * tiling, else 0.
  * The tiling is a scene property: cotix_scene_create(_ex) sets the default to
  * 4 envs per wave, or the largest of 2 and 1 whose workgroup (the hot tables
  * + 4 wave tiles and scratches) fits the CU's 160 KiB of LDS; a scene whose

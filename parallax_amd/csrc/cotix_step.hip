@@ -20,8 +20,6 @@
 #include "cotix_scene.h"
 
 using cxk::FNS_ANALYTIC;
-using cxk::FNS_CIRCLE_POLY;
-using cxk::FNS_CONVEX;
 using cxk::SceneDev;
 
 namespace {
@@ -50,39 +48,10 @@ struct cotix_scene {
   // the form of the last step launch (cotix_scene_last_step_form)
   int last_step_form = 0;
 };
-// a workgroup's LDS at `ew` envs per wave and `wpb` waves (cxk::lds_bytes:
-// the hot tables + wpb tiles and wave scratches) and the hardware's 160 KiB
-// per CU
-constexpr size_t LDS_CAP = 160 * 1024;
-static size_t scene_lds_w(const cotix_scene* sc, int ew, int wpb) { return cxk::lds_bytes(sc->host, wpb, ew); }
-// waves per workgroup of a tiling: WPB (one per SIMD), or for a scene whose
-// tiles do not fit four at a time 2, then 1 -- a workgroup of one wave holds
-// one tile and the tables; 0: not even that fits (the scene's hard cap)
-static int scene_wpb(const cotix_scene* sc, int ew) {
-  for (int w : {cxl::WPB, 2, 1})
-    if (scene_lds_w(sc, ew, w) <= LDS_CAP) return w;
-  return 0;
-}
-static size_t scene_lds(const cotix_scene* sc, int ew) {
-  const int w = scene_wpb(sc, ew);
-  return scene_lds_w(sc, ew, w ? w : 1);
-}
-// the default tiling of a scene: 4 envs per wave (the measured best), else
-// the largest of 2, 1 whose workgroup of WPB waves fits the LDS, else one env
-// per wave in workgroups of 2 or 1 waves; 0: none fits
-static int lds_default_ew(const cotix_scene* sc) {
-#ifdef COTIX_EW4_ONLY
-  return scene_lds_w(sc, 4, cxl::WPB) <= LDS_CAP ? 4 : 0;
-#else
-  for (int ew : {4, 2, 1})
-    if (scene_lds_w(sc, ew, cxl::WPB) <= LDS_CAP) return ew;
-  return scene_wpb(sc, 1) ? 1 : 0;
-#endif
-}
-// the specialization a launch of this scene uses (cxk::SPEC_*)
-static int scene_spec(const cotix_scene* scene) {
-  return scene->specialize ? cxk::spec_of(scene->host) : cxk::SPEC_GENERIC;
-}
+// the tilings and the launch plan are cotix_plan.h's (cxl::)
+using cxl::LDS_CAP;
+using cxl::lds_default_ew;
+using cxl::scene_wpb;
 
 namespace {
 
@@ -295,9 +264,9 @@ int cotix_scene_create_ex2(int n_bodies, const float* body_params, int n_parts, 
   }
   // the tiling is a property of the scene: a scene whose tile does not fit
   // the LDS even at one env per wave is rejected here, not at its first launch
-  sc->envs_per_wave = lds_default_ew(sc);
+  sc->envs_per_wave = lds_default_ew(sc->host);
   if (sc->envs_per_wave == 0) {
-    const size_t need = scene_lds_w(sc, 1, 1);
+    const size_t need = cxk::lds_bytes(sc->host, 1, 1);
     delete sc;
     return fail("scene too large for the LDS tile: " + std::to_string(need) + " bytes for one env's tile and the "
                 "tables (a workgroup of one wave), the CU has " + std::to_string(LDS_CAP));
@@ -332,15 +301,15 @@ int cotix_scene_destroy(cotix_scene* scene) {
 
 int cotix_scene_set_variant(cotix_scene* scene, int envs_per_wave, int specialize) {
   if (!scene) return fail("null scene");
-  if (envs_per_wave == 0) envs_per_wave = lds_default_ew(scene);
+  if (envs_per_wave == 0) envs_per_wave = lds_default_ew(scene->host);
   if (envs_per_wave != 1 && envs_per_wave != 2 && envs_per_wave != 4 && envs_per_wave != 8)
     return fail("envs_per_wave must be 0 (default), 1, 2, 4 or 8");
 #ifdef COTIX_EW4_ONLY
   if (envs_per_wave != 4) return fail("this build carries the 4-envs-per-wave tiling only");
 #endif
-  if (scene_wpb(scene, envs_per_wave) == 0)
+  if (scene_wpb(scene->host, envs_per_wave) == 0)
     return fail("envs_per_wave " + std::to_string(envs_per_wave) + ": the scene's workgroup needs " +
-                std::to_string(scene_lds(scene, envs_per_wave)) + " bytes of LDS, the CU has " +
+                std::to_string(cxk::lds_bytes(scene->host, 1, envs_per_wave)) + " bytes of LDS, the CU has " +
                 std::to_string(LDS_CAP));
   scene->envs_per_wave = envs_per_wave;
   scene->specialize = specialize ? 1 : 0;
@@ -354,19 +323,17 @@ int cotix_scene_last_step_form(cotix_scene* scene) {
 
 int cotix_scene_waves_per_group(const cotix_scene* scene) {
   if (!scene) return fail("null scene");
-  return scene_wpb(scene, scene->envs_per_wave);
+  return scene_wpb(scene->host, scene->envs_per_wave);
 }
 
 int cotix_scene_variant(const cotix_scene* scene, int* envs_per_wave, int* spec) {
   if (!scene) return fail("null scene");
   if (envs_per_wave) *envs_per_wave = scene->envs_per_wave;
-  // the step program's specialization, as the launcher has it
-  // (cotix_step_kernel.hip): the reference scenes at 4 and 2 envs per wave,
-  // the box world's structure at 4 only
-  if (spec) {
-    const int ew = scene->envs_per_wave, s = scene_spec(scene);
-    *spec = (ew == 4 || (ew == 2 && s != cxk::SPEC_BOX)) ? s : cxk::SPEC_GENERIC;
-  }
+  // the step program's specialization: the plan of a one-step launch
+  if (spec)
+    *spec = cxl::plan_launch(scene->host, scene->fnset, {scene->envs_per_wave, scene->specialize}, cxk::KArgs{}, 0,
+                             cxl::Device{0, false, false})
+                .spec;
   return 0;
 }
 
@@ -430,17 +397,10 @@ static int device_cus() {
   }();
   return n;
 }
-// launch the fused step kernel (mode 0 step, 1 rollout forward, 2 backward re-play, 3 eval with a judge/control)
+// launch the fused step kernel (mode 0 step, 1 rollout forward, 2 backward re-play, 3 eval with a judge/control,
+// 4 tape backward): the kernel, grid, block and LDS bytes are the plan's (cotix_plan.h)
 static int launch(cotix_scene* scene, const cxk::KArgs& ka0, int mode, cotix_stream_t stream) {
   if (scene_upload(scene)) return -1;
-#ifdef COTIX_EW4_ONLY
-  const int EW = 4;
-#else
-  const int EW = scene->envs_per_wave;
-#endif
-  const int wpb = scene_wpb(scene, EW);
-  if (wpb == 0) return fail("scene too large for the LDS tile");  // (not reached: checked at create / set_variant)
-  const size_t lds = scene_lds_w(scene, EW, wpb);
   cxk::KArgs ka = ka0;
   ka.sc = scene->dev;
   ka.sh = scene->host;  // the header by value (kernel arguments)
@@ -448,59 +408,26 @@ static int launch(cotix_scene* scene, const cxk::KArgs& ka0, int mode, cotix_str
   const char* dbg = getenv("COTIX_DEBUG_SKIP");
   ka.dbg_skip = dbg ? atoi(dbg) : 0;
 #endif
+  const cxl::LaunchPlan plan =
+      cxl::plan_launch(scene->host, scene->fnset, {scene->envs_per_wave, scene->specialize}, ka, mode,
+                       cxl::Device{device_cus(), key_helper_enabled(), split_bwd_enabled()});
+  if (plan.error) return fail(plan.error);
+  if (mode == 0) scene->last_step_form = plan.family;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const int fs = scene->fnset;
-  // scene specialization (compile-time dimensions; reference scenes, whose
-  // tiles always fit WPB to a workgroup)
-  const int spec = wpb == cxl::WPB ? scene_spec(scene) : cxk::SPEC_GENERIC;
-  // the tape backward at two waves per env group where the scene allows it
-  // and two tiles per group fit (cxk::run_backward_split; the same bits).
-  // A launch that asks for the body parameters' gradient runs the one-wave
-  // MODE 4 (the consumer chain does not carry them)
-  if (mode == 4 && EW == 4 && wpb == cxl::WPB && split_bwd_enabled() && ka.grad_params == nullptr &&
-      cxk::launch_fnset(fs, mode) == cxk::FNS_ANALYTIC &&
-      cxk::split_bwd_ok<4>(ka, cxk::make_ctx<4>(scene->host)) &&
-      scene_lds_w(scene, 4, 2 * cxl::WPB) <= LDS_CAP) {
-    const int r = cxl::launch_bwd_split(ka, spec, scene_lds_w(scene, 4, 2 * cxl::WPB), st);
-    if (r == 0) return hip_check(hipGetLastError(), "bwd_split_kernel launch");
-  }
-  // the step program with a key-window helper wave per env group where the
-  // launch has more than one key window (cxk::KeyHelper; the same bits)
-  if (mode == 0 && EW == 4 && wpb == cxl::WPB && ka.n_steps > cxk::KWIN && key_helper_enabled() &&
-      cxk::launch_fnset(fs, mode) == cxk::FNS_ANALYTIC &&
-      cxk::help_lds_bytes<4>(scene->host, cxl::WPB) <= LDS_CAP) {
-    // with the level-1 key ring (cxk::KeyL1) where the scan is the fused one
-    // that reads it, the ring fits, and its LDS costs the launch no residency:
-    // a CU holds two of these workgroups by its registers (__launch_bounds__
-    // of 512 threads) and LDS_CAP / lds by its LDS, and the launch needs no
-    // more than its workgroups over the CUs
-    const size_t lds0 = cxk::help_lds_bytes<4>(scene->host, cxl::WPB);
-    const size_t lds1 =
-        cxk::help_l1_lds_bytes<4>(scene->host, cxl::WPB, cxk::key_l1_keys(scene->host, scene->host.hot));
-    const cxk::Ctx c4 = cxk::make_ctx<4>(scene->host);
-    const int cus = device_cus(), wgs = (ka.B + 4 * cxl::WPB - 1) / (4 * cxl::WPB);
-    const int need = cus > 0 ? (wgs + cus - 1) / cus : 2;
-    const int res0 = std::min<int>(2, (int)(LDS_CAP / lds0)), res1 = std::min<int>(2, (int)(LDS_CAP / lds1));
-    const bool l1 = (ka.stages & COTIX_STAGE_COLLIDER) && c4.nl > 0 && cxk::scan_fused<4>(c4) && lds1 <= LDS_CAP &&
-                    res1 >= std::min(res0, need);
-    const int r = cxl::launch_step_help(ka, spec, l1 ? lds1 : lds0, st, l1);
-    if (r == 0) {
-      scene->last_step_form = l1 ? 2 : 1;
-      return hip_check(hipGetLastError(), "step_help_kernel launch");
-    }
-  }
-  if (mode == 0) scene->last_step_form = 0;
   hipError_t e;
 #ifdef COTIX_EW4_ONLY  // tooling builds (phase profile, ISA markers): the default tiling only
-  e = cxl::launch_step_ew4(ka, fs, mode, lds, st, spec, wpb);
+  e = cxl::launch_ew4(plan, ka, st);
 #else
-  if (EW == 1) e = cxl::launch_step_ew1(ka, fs, mode, lds, st, spec, wpb);
-  else if (EW == 2) e = cxl::launch_step_ew2(ka, fs, mode, lds, st, spec, wpb);
-  else if (EW == 8) e = cxl::launch_step_ew8(ka, fs, mode, lds, st, spec, wpb);
-  else e = cxl::launch_step_ew4(ka, fs, mode, lds, st, spec, wpb);
+  if (plan.ew == 1) e = cxl::launch_ew1(plan, ka, st);
+  else if (plan.ew == 2) e = cxl::launch_ew2(plan, ka, st);
+  else if (plan.ew == 8) e = cxl::launch_ew8(plan, ka, st);
+  else e = cxl::launch_ew4(plan, ka, st);
 #endif
-  if (e != hipSuccess) return hip_check(e, "step_kernel launch");
-  return hip_check(hipGetLastError(), "step_kernel launch");
+  const char* what = plan.family == cxl::FAM_SPLIT  ? "bwd_split_kernel launch"
+                     : plan.family == cxl::FAM_STEP ? "step_kernel launch"
+                                                    : "step_help_kernel launch";
+  if (e != hipSuccess) return hip_check(e, what);
+  return hip_check(hipGetLastError(), what);
 }
 
 static int step_impl(cotix_scene* scene, float* dyn, uint32_t* keys, uint32_t* err, const float* geom,

@@ -1,7 +1,11 @@
 // cotix_step_kernel.hip -- the fused step kernel (gfx950) for ONE envs-per-wave
-// tiling: compiled once per EW with -DCOTIX_EW=N (see cotix_launch.h); the
-// phase programs live in cotix_kernel.h, design notes there and in DESIGN.md.
+// tiling: compiled once per EW with -DCOTIX_EW=N (see cotix_launch.h), the
+// instantiations cotix_plan.h lists for that EW; the phase programs live in
+// cotix_kernel.h, design notes there and in DESIGN.md.
 #include <hip/hip_runtime.h>
+
+#include <array>
+#include <utility>
 
 #include "../../include/cotix_amd.h"
 #include "cotix_device.h"
@@ -12,9 +16,6 @@
 #error "compile with -DCOTIX_EW=1|2|4|8"
 #endif
 
-using cxk::FNS_ANALYTIC;
-using cxk::FNS_CIRCLE_POLY;
-using cxk::FNS_CONVEX;
 using cxk::SceneDev;
 
 namespace {
@@ -53,7 +54,8 @@ struct WaveRun {
     });
   }
 #ifdef COTIX_PHASE_PROF
-  unsigned long long* acc;  // per-phase cycle accumulators (registers after inlining)
+  unsigned long long* acc;  // per-phase cycle accumulators (registers after inlining); set by every kernel
+  __device__ __forceinline__ WaveRun(int l, unsigned long long* a) : lane(l), acc(a) {}
   template <class F>
   __device__ __forceinline__ void operator()(int ph, F f) const {
     const unsigned long long t0 = clock64();
@@ -80,6 +82,26 @@ struct WaveRun {
   }
 #endif
 };
+// a wave's phase runner and, in the phase-profile build, its per-phase cycle
+// accumulators: flushed to g_phase_cycles by lane 0 of the waves that ran phases
+#ifdef COTIX_PHASE_PROF
+struct PhaseAcc {
+  unsigned long long acc[cxk::PH_COUNT];
+  __device__ __forceinline__ WaveRun run(int lane) {
+    for (int q = 0; q < cxk::PH_COUNT; ++q) acc[q] = 0ull;
+    return WaveRun{lane, acc};
+  }
+  __device__ __forceinline__ void flush(bool on) const {
+    if (on)
+      for (int q = 0; q < cxk::PH_COUNT; ++q) atomicAdd(&g_phase_cycles[q], acc[q]);
+  }
+};
+#else
+struct PhaseAcc {
+  __device__ __forceinline__ WaveRun run(int lane) const { return WaveRun{lane}; }
+  __device__ __forceinline__ void flush(bool) const {}
+};
+#endif
 // MODE 0: step, 1: rollout forward (saves + return, + tape), 2: rollout
 // backward re-playing the forward, 3: eval with the device judge / control
 // (cotix_eval), 4: rollout backward from the forward's tape;
@@ -94,13 +116,11 @@ __global__ __launch_bounds__(WPB * 64) void step_kernel(cxk::KArgs a) {
   const SceneDev* sc = a.sc;
   const cxk::SceneHdr sh = cxk::spec_hdr<SPEC>(a.sh);  // a constant for SPEC > 0
   const int nhot = sh.nhot;
-  // the scene tables into LDS: HC reads per thread issued before any store
-  // (one global round trip per HC * 256 words, not one per 256)
-  constexpr int HC = 16;
   // waves in this workgroup: WPB, or 2 / 1 for scenes whose tiles do not fit
   // four at a time (generic kernel only: the specializations are the
   // reference scenes, which fit, and keep their folded constants)
   const int nw = SPEC != cxk::SPEC_GENERIC ? WPB : (int)blockDim.x >> 6;
+  constexpr int HC = 16;
   const int nt = nw * 64;
   for (int base = 0; base < nhot; base += HC * nt) {
     uint32_t r[HC];
@@ -136,13 +156,8 @@ __global__ __launch_bounds__(WPB * 64) void step_kernel(cxk::KArgs a) {
   __syncthreads();
   CXK_STAMP(st2);
   if (env0 >= a.B) return;  // whole wave idle (after the only workgroup barrier)
-#ifdef COTIX_PHASE_PROF
-  unsigned long long acc[cxk::PH_COUNT];
-  for (int q = 0; q < cxk::PH_COUNT; ++q) acc[q] = 0ull;
-  const WaveRun run{lane, acc};
-#else
-  const WaveRun run{lane};
-#endif
+  PhaseAcc pa;
+  const WaveRun run = pa.run(lane);
   if (MODE == 4)
     cxk::run_wave_backward_tape<EW, FNSET, GP>(a, c, t, env0, run);
   else if (MODE == 2)
@@ -152,9 +167,8 @@ __global__ __launch_bounds__(WPB * 64) void step_kernel(cxk::KArgs a) {
   else
     cxk::run_wave<EW, FNSET, MODE == 1, false,
                   MODE == 0 && (SPEC == cxk::SPEC_ROBOCUP || SPEC == cxk::SPEC_ROBOCUP_PART)>(a, c, t, env0, run, true);
+  pa.flush(lane == 0);
 #ifdef COTIX_PHASE_PROF
-  if (lane == 0)
-    for (int q = 0; q < cxk::PH_COUNT; ++q) atomicAdd(&g_phase_cycles[q], acc[q]);
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
   CXK_STAMP(st3);
   const int gw = (int)blockIdx.x * nw + wave;
@@ -200,24 +214,17 @@ __global__ __launch_bounds__(2 * WPB * 64) void bwd_split_kernel(cxk::KArgs a) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int grp = wave % WPB, role = wave < WPB ? 1 : 2;
   const int env0 = (blockIdx.x * WPB + grp) * EW;
-  const int rw = c.L.S * EW + c.W.words;  // one wave's region: tile + scratch
+  // the group's two tiles are its two waves' regions; each wave keeps its own scratch
+  const int rw = c.L.S * EW + c.W.words;
   uint32_t* r0 = lds + nhot + grp * rw;
   uint32_t* r1 = lds + nhot + (grp + WPB) * rw;
   uint32_t* ws = (role == 1 ? r0 : r1) + c.L.S * EW;
   const cxk::Tile<EW> t0{r0, lds, ws}, t1{r1, lds, ws};
   __syncthreads();
-#ifdef COTIX_PHASE_PROF
-  unsigned long long acc[cxk::PH_COUNT];
-  for (int q = 0; q < cxk::PH_COUNT; ++q) acc[q] = 0ull;
-  const WaveRun run{lane, acc};
-#else
-  const WaveRun run{lane};
-#endif
+  PhaseAcc pa;
+  const WaveRun run = pa.run(lane);
   cxk::run_backward_split<EW, NB>(a, c, t0, t1, env0, run, role, [] { lds_barrier(); });
-#ifdef COTIX_PHASE_PROF
-  if (lane == 0 && env0 < a.B)
-    for (int q = 0; q < cxk::PH_COUNT; ++q) atomicAdd(&g_phase_cycles[q], acc[q]);
-#endif
+  pa.flush(lane == 0 && env0 < a.B);
 }
 // the step program with a key-window helper wave per env group
 // (cxk::KeyHelper): waves g < WPB step env group g, wave g + WPB computes its
@@ -269,7 +276,8 @@ __global__ __launch_bounds__(2 * WPB * 64) void step_help_kernel(cxk::KArgs a) {
   const cxk::Tile<EW> tm{um, lds, um + c.L.S * EW};
   if (stepper && env0 < a.B) cxk::ph_load_fwd<EW, false>(a, c, tm, env0, lane);
   __syncthreads();
-  const WaveRun run{lane};
+  PhaseAcc pa;
+  const WaveRun run = pa.run(lane);
   const int nbar = L1 ? cxk::key_l1_barriers(a) : cxk::keys_on(a) ? cxk::key_helper_windows(a) : 0;
   if (env0 >= a.B) {  // an idle wave keeps the barrier count
     for (int q = 0; q < nbar; ++q) lds_barrier();
@@ -311,155 +319,67 @@ __global__ __launch_bounds__(2 * WPB * 64) void step_help_kernel(cxk::KArgs a) {
       lds_barrier();
     }
   }
+  pa.flush(lane == 0 && stepper);  // the step waves' phases (the helper's K work overlaps them)
 }
 #endif
+
+// ---------------------------------------------------------------------------
+// the kernels of this tiling: one function pointer per entry of cotix_plan.h's
+// lists (null where the entry is not compiled for this EW, and then not
+// instantiated), in the lists' order
+// ---------------------------------------------------------------------------
+using KernelFn = void (*)(cxk::KArgs);
+template <int EW, size_t I>
+constexpr KernelFn step_fn() {
+  constexpr cxl::StepKey k = cxl::STEP_KERNELS[I];
+  if constexpr ((k.ews & EW) != 0)
+    return &step_kernel<EW, k.fnset, k.mode, k.spec, k.gp>;
+  else
+    return nullptr;
+}
+template <int EW, size_t... I>
+constexpr std::array<KernelFn, sizeof...(I)> step_fns(std::index_sequence<I...>) {
+  return {step_fn<EW, I>()...};
+}
+#if COTIX_EW == 4
+template <size_t... I>
+constexpr std::array<KernelFn, sizeof...(I)> help_fns(std::index_sequence<I...>) {
+  return {&step_help_kernel<cxl::HELP_KERNELS[I].fnset, cxl::HELP_KERNELS[I].spec, cxl::HELP_KERNELS[I].sdefer,
+                            cxl::HELP_KERNELS[I].l1>...};
+}
+template <size_t... I>
+constexpr std::array<KernelFn, sizeof...(I)> split_fns(std::index_sequence<I...>) {
+  return {&bwd_split_kernel<cxl::SPLIT_KERNELS[I].nb, cxl::SPLIT_KERNELS[I].spec>...};
+}
+#endif
+template <class K, size_t N>
+KernelFn kernel_of(const K (&list)[N], const std::array<KernelFn, N>& fns, const K& key) {
+  const int i = cxl::kernel_index(list, COTIX_EW, key);
+  return i < 0 ? nullptr : fns[i];
+}
 
 }  // namespace
 
-#if COTIX_EW == 4
-// 0: launched; 1: not compiled for this scene / launch (the caller launches step_kernel)
-int cxl::launch_step_help(const cxk::KArgs& ka, int spec, size_t lds, hipStream_t st, bool l1) {
-  const dim3 grid((ka.B + WPB * 4 - 1) / (WPB * 4)), block(2 * WPB * 64);
-  if (spec == cxk::SPEC_ROBOCUP && l1)
-    hipLaunchKernelGGL((step_help_kernel<FNS_ANALYTIC, cxk::SPEC_ROBOCUP, true, true>), grid, block, lds, st, ka);
-  else if (spec == cxk::SPEC_ROBOCUP)
-    hipLaunchKernelGGL((step_help_kernel<FNS_ANALYTIC, cxk::SPEC_ROBOCUP, true>), grid, block, lds, st, ka);
-  else
-    return 1;
-  return 0;
-}
-// 0: launched; 1: not this scene / launch (the caller runs MODE 4)
-int cxl::launch_bwd_split(const cxk::KArgs& ka, int spec, size_t lds, hipStream_t st) {
-  const dim3 grid((ka.B + WPB * 4 - 1) / (WPB * 4)), block(2 * WPB * 64);
-  const int nb = ka.sh.nb;
-#define COTIX_LAUNCH_SPLIT(NB, SP) hipLaunchKernelGGL((bwd_split_kernel<NB, SP>), grid, block, lds, st, ka)
-  // the specializations only: with the header's dimensions as run-time
-  // values the two roles' registers exceed 256 VGPRs and spill (the generic
-  // scenes keep MODE 4)
-  if (spec == cxk::SPEC_ROBOCUP && nb == 5)
-    COTIX_LAUNCH_SPLIT(5, cxk::SPEC_ROBOCUP);
-  // (the box world's split form is compiled and emulation-tested but not
-  // launched: measured slower than its one-wave MODE 4, 0.55 against 0.42 ms
-  // per 64-step backward)
-  else
-    return 1;
-#undef COTIX_LAUNCH_SPLIT
-  return 0;
-}
-#endif
-
-#define CXL_NAME2(n) launch_step_ew##n
+// the plan's kernel launched as planned; a key that is not in this tiling's
+// table is an error (the plan has already fallen back)
+#define CXL_NAME2(n) launch_ew##n
 #define CXL_NAME(n) CXL_NAME2(n)
-hipError_t cxl::CXL_NAME(COTIX_EW)(const cxk::KArgs& ka, int fs, int mode, size_t lds, hipStream_t st, int spec,
-                                   int wpb) {
-  constexpr int EW = COTIX_EW;
-  if ((wpb != 1 && wpb != 2 && wpb != WPB) || (wpb != WPB && spec != cxk::SPEC_GENERIC)) return hipErrorInvalidValue;
-  const dim3 grid((ka.B + wpb * EW - 1) / (wpb * EW)), block(wpb * 64);
-#define COTIX_LAUNCH(FS, BW) hipLaunchKernelGGL((step_kernel<EW, FS, BW>), grid, block, lds, st, ka)
-#define COTIX_LAUNCH_SPEC(FS, BW, SP) hipLaunchKernelGGL((step_kernel<EW, FS, BW, SP>), grid, block, lds, st, ka)
-  constexpr int F_AN = FNS_ANALYTIC, F_PP = FNS_ANALYTIC | FNS_CONVEX, F_AP = F_PP | cxk::FNS_AABB_POLY,
-                F_ALL = F_AP | FNS_CIRCLE_POLY;
-  const int F = cxk::launch_fnset(fs, mode);  // the contact-function program for this scene
-  // the backward with the body parameters' gradient: the generic one-wave
-  // programs, and the tape backward of RoboCup's and the box world's
-  // specializations at the default tiling
-  if (ka.grad_params != nullptr) {
-    if (mode != 2 && mode != 4) return hipErrorInvalidValue;
-#define COTIX_LAUNCH_GP(FS, BW, SP) \
-  hipLaunchKernelGGL((step_kernel<EW, FS, BW, SP, true>), grid, block, lds, st, ka)
+hipError_t cxl::CXL_NAME(COTIX_EW)(const cxl::LaunchPlan& p, const cxk::KArgs& ka, hipStream_t st) {
+  static constexpr auto STEP = step_fns<COTIX_EW>(std::make_index_sequence<std::size(cxl::STEP_KERNELS)>{});
+  KernelFn fn = nullptr;
+  if (p.ew != COTIX_EW || p.error != nullptr) return hipErrorInvalidValue;
+  if (p.family == cxl::FAM_STEP) fn = kernel_of(cxl::STEP_KERNELS, STEP, cxl::step_key(p));
 #if COTIX_EW == 4
-    if (mode == 4 && F == F_AN && spec == cxk::SPEC_ROBOCUP)
-      COTIX_LAUNCH_GP(F_AN, 4, cxk::SPEC_ROBOCUP);
-    else if (mode == 4 && F == F_AN && spec == cxk::SPEC_BOX)
-      COTIX_LAUNCH_GP(F_AN, 4, cxk::SPEC_BOX);
-    else
+  static constexpr auto HELP = help_fns(std::make_index_sequence<std::size(cxl::HELP_KERNELS)>{});
+  static constexpr auto SPLIT = split_fns(std::make_index_sequence<std::size(cxl::SPLIT_KERNELS)>{});
+  if (p.family == cxl::FAM_HELP || p.family == cxl::FAM_HELP_L1)
+    fn = kernel_of(cxl::HELP_KERNELS, HELP, cxl::help_key(p));
+  if (p.family == cxl::FAM_SPLIT) fn = kernel_of(cxl::SPLIT_KERNELS, SPLIT, cxl::split_key(p));
 #endif
-    if (mode == 4 && F == F_AN)
-      COTIX_LAUNCH_GP(F_AN, 4, cxk::SPEC_GENERIC);
-    else if (mode == 4)
-      COTIX_LAUNCH_GP(F_ALL, 4, cxk::SPEC_GENERIC);
-    else if (F == F_AN)
-      COTIX_LAUNCH_GP(F_AN, 2, cxk::SPEC_GENERIC);
-    else
-      COTIX_LAUNCH_GP(F_ALL, 2, cxk::SPEC_GENERIC);
-#undef COTIX_LAUNCH_GP
-    return hipGetLastError();
-  }
-#if COTIX_EW == 4 || COTIX_EW == 2
-  // the reference-scene specializations: every program of RoboCup at the
-  // default tiling, the step programs (mode 0) at 4 and 2 envs per wave
-  // (the re-play backward, mode 2, is the tape backward's check: generic only)
-  if (spec == cxk::SPEC_ROBOCUP && F == F_AN && mode != 2 && (mode == 0 || COTIX_EW == 4)) {
-    if (mode == 3)
-      COTIX_LAUNCH_SPEC(F_AN, 3, cxk::SPEC_ROBOCUP);
-    else if (mode == 4)
-      COTIX_LAUNCH_SPEC(F_AN, 4, cxk::SPEC_ROBOCUP);
-    else if (mode == 1)
-      COTIX_LAUNCH_SPEC(F_AN, 1, cxk::SPEC_ROBOCUP);
-    else
-      COTIX_LAUNCH_SPEC(F_AN, 0, cxk::SPEC_ROBOCUP);
-    return hipGetLastError();
-  }
-  if (spec == cxk::SPEC_LUNAR && mode == 0 && F == F_PP) {
-    COTIX_LAUNCH_SPEC(F_PP, 0, cxk::SPEC_LUNAR);
-    return hipGetLastError();
-  }
-#if COTIX_EW == 4
-  // the box world's structure: the step and rollout programs (finite_scene, grad_box)
-  if (spec == cxk::SPEC_BOX && F == F_AN && (mode <= 1 || mode == 4)) {
-    if (mode == 4)
-      COTIX_LAUNCH_SPEC(F_AN, 4, cxk::SPEC_BOX);
-    else if (mode == 1)
-      COTIX_LAUNCH_SPEC(F_AN, 1, cxk::SPEC_BOX);
-    else
-      COTIX_LAUNCH_SPEC(F_AN, 0, cxk::SPEC_BOX);
-    return hipGetLastError();
-  }
-#endif
-  // the partitionable layout's specializations: the step program only
-  if (spec == cxk::SPEC_ROBOCUP_PART && mode == 0 && F == F_AN) {
-    COTIX_LAUNCH_SPEC(F_AN, 0, cxk::SPEC_ROBOCUP_PART);
-    return hipGetLastError();
-  }
-  if (spec == cxk::SPEC_LUNAR_PART && mode == 0 && F == F_PP) {
-    COTIX_LAUNCH_SPEC(F_PP, 0, cxk::SPEC_LUNAR_PART);
-    return hipGetLastError();
-  }
-#else
-  (void)spec;
-#endif
-#undef COTIX_LAUNCH_SPEC
-  if (mode == 2) {
-    if (F == F_AN)
-      COTIX_LAUNCH(F_AN, 2);
-    else
-      COTIX_LAUNCH(F_ALL, 2);  // polygon scenes (the host rejects circle x polygon contacts)
-  } else if (mode == 4) {
-    if (F == F_AN)
-      COTIX_LAUNCH(F_AN, 4);
-    else
-      COTIX_LAUNCH(F_ALL, 4);
-  } else if (mode == 3) {
-    if (F == F_AN)
-      COTIX_LAUNCH(F_AN, 3);
-    else
-      COTIX_LAUNCH(F_ALL, 3);
-  } else if (mode == 1) {
-    if (F == F_AN)
-      COTIX_LAUNCH(F_AN, 1);
-    else
-      COTIX_LAUNCH(F_ALL, 1);
-  } else if (F == F_AN) {
-    COTIX_LAUNCH(F_AN, 0);
-  } else if (F == F_PP) {
-    COTIX_LAUNCH(F_PP, 0);
-  } else if (F == F_AP) {
-    COTIX_LAUNCH(F_AP, 0);
-  } else {
-    COTIX_LAUNCH(F_ALL, 0);
-  }
-#undef COTIX_LAUNCH
-  return hipGetLastError();
+  if (fn == nullptr) return hipErrorInvalidValue;
+  cxk::KArgs a = ka;
+  void* args[] = {&a};
+  return hipLaunchKernel(reinterpret_cast<const void*>(fn), dim3(p.grid), dim3(p.block), args, p.lds, st);
 }
 
 #ifdef COTIX_PHASE_PROF

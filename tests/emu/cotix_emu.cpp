@@ -16,6 +16,7 @@
 
 #include "../../parallax_amd/csrc/cotix_body.h"
 #include "../../parallax_amd/csrc/cotix_kernel.h"
+#include "../../parallax_amd/csrc/cotix_plan.h"
 #include "../../parallax_amd/csrc/cotix_scene.h"
 #include "cotix_simt.h"
 
@@ -127,10 +128,8 @@ void run_blocks(const cxk::KArgs& a, int mode) {
   }
 }
 void run_any(const cxk::KArgs& a, int E, int mode) {
-  // the GPU's key helper (cotix_step.hip launch) where it applies and is asked for
-  if (mode == 0 && g_key_helper && E == 4 && a.n_steps > cxk::KWIN &&
-      cxk::launch_fnset(a.sc->fnset, 0) == cxk::FNS_ANALYTIC)
-    mode = 6;
+  // the GPU's key helper where its wave program may run and it is asked for
+  if (mode == 0 && g_key_helper && cxl::key_helper_may_run(a.sc->fnset, E, a.n_steps)) mode = 6;
   if (E == 1) run_blocks<1>(a, mode);
   else if (E == 4) run_blocks<4>(a, mode);
   else if (E == 8) run_blocks<8>(a, mode);
@@ -314,20 +313,21 @@ int emu_rollout_backward(void* scene, const float* saved_dyn, const uint32_t* sa
   a.grad_action = grad_action;
   a.grad_dyn = grad_dyn0;
   for (int k = 0; k < s->s.nb * 6; ++k) a.ret_w[k] = ret_w[k];
-  // the GPU's split backward (cotix_step.hip launch) where it applies and is asked for
-  const bool split = g_split_bwd && tape && E == 4 && cxk::launch_fnset(s->fnset, 4) == cxk::FNS_ANALYTIC &&
-                     cxk::split_bwd_ok<4>(a, cxk::make_ctx<4>(s->s));
+  // the GPU's split backward where its wave program may run and it is asked for
+  const bool split = g_split_bwd && cxl::split_bwd_may_run(s->s, s->fnset, E, a);
   run_any(a, E, tape ? (split ? 5 : 4) : 2);
   return 0;
 }
 // 1: the step launches run the step program with the key helper
-// (run_wave + KeyHelper) where the library would; 0 (default): run_wave alone
+// (run_wave + KeyHelper) on every launch that admits it
+// (cxl::key_helper_may_run); 0 (default): run_wave alone
 int emu_set_key_helper(int on) {
   g_key_helper = on != 0;
   return 0;
 }
 // 1: emu_rollout_backward runs the split tape backward (run_backward_split)
-// where the library would; 0 (default): run_wave_backward_tape
+// on every launch that admits it (cxl::split_bwd_may_run); 0 (default):
+// run_wave_backward_tape
 int emu_set_split_bwd(int on) {
   g_split_bwd = on != 0;
   return 0;
@@ -518,7 +518,7 @@ extern "C" int emu_scene_dims(void* scene, int* out) {
   for (int k = 0; k < 13; ++k) out[k] = v[k];
   return 13;
 }
-// the step-kernel specialization the launcher picks for the scene (cxk::spec_of)
+// the scene's specialization (cxk::spec_of; the launch plan uses it where its kernel is compiled)
 extern "C" int emu_scene_spec(void* scene) { return cxk::spec_of(static_cast<EmuScene*>(scene)->s); }
 
 // the scene's header as a C++ initializer in declaration order (floats as
@@ -558,6 +558,32 @@ extern "C" long emu_lds_bytes(void* scene, int ew) {
 }
 extern "C" long emu_lds_bytes_w(void* scene, int ew, int wpb) {
   return (long)cxk::lds_bytes(static_cast<EmuScene*>(scene)->s, wpb, ew);
+}
+// the library's launch plan (cxl::plan_launch) for the scene and the plan's
+// inputs; grad_params: the launch asks for the body parameters' gradient.
+// out: family, ew, wpb, fnset, mode, spec, gp, sdefer, nb, grid, block, lds
+// bytes, error (0 / 1), whether the plan's key is in the kernel list (0 / 1)
+extern "C" int emu_launch_plan(void* scene, int envs_per_wave, int specialize, int mode, int B, int n_steps,
+                               int stages, int grad_params, int cus, int key_helper_on, int split_bwd_on,
+                               long* out) {
+  const EmuScene* s = static_cast<EmuScene*>(scene);
+  static uint32_t tape;  // (never read: the plan looks at the pointers only)
+  static float gp;
+  cxk::KArgs a{};
+  a.B = B;
+  a.n_steps = n_steps;
+  a.stages = mode == 2 || mode == 4 ? stages & ~COTIX_STAGE_BROADPHASE : stages;  // (the library's backward)
+  a.tape = mode == 4 ? &tape : nullptr;
+  a.grad_params = grad_params ? &gp : nullptr;
+  const cxl::LaunchPlan p = cxl::plan_launch(s->s, s->fnset, {envs_per_wave, specialize}, a, mode,
+                                             cxl::Device{cus, key_helper_on != 0, split_bwd_on != 0});
+  const bool listed = p.family == cxl::FAM_STEP    ? cxl::compiled(p.ew, cxl::step_key(p))
+                      : p.family == cxl::FAM_SPLIT ? cxl::compiled(p.ew, cxl::split_key(p))
+                                                   : cxl::compiled(p.ew, cxl::help_key(p));
+  const long v[] = {p.family, p.ew,    p.wpb,  p.fnset,     p.mode,      p.spec,      p.gp,
+                    p.sdefer, p.nb,    p.grid, p.block, (long)p.lds, p.error != nullptr, listed};
+  for (int k = 0; k < 14; ++k) out[k] = v[k];
+  return 14;
 }
 
 // circle x polygon: the gradient's recorded re-run (cx::cp_forward) against

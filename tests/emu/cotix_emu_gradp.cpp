@@ -14,7 +14,8 @@ void run_blocks_gp(const cxk::KArgs& a, bool tape) {
   const int nwaves = (a.B + EW - 1) / EW;
   std::vector<uint32_t> lds((size_t)sc.nhot + (size_t)cxk::help_region_words<EW>(c));
   for (int q = 0; q < sc.nhot; ++q) lds[q] = sc.hot[q];
-  const int F = cxk::launch_fnset(sc.fnset, tape ? 4 : 2);  // the kernel instantiation the library launches
+  // the plan's contact-function program (a launch with grad_params is never the split form)
+  const int F = cxk::launch_fnset(sc.fnset, tape ? 4 : 2);
   for (int wv = 0; wv < nwaves; ++wv) {
     std::fill(lds.begin() + sc.nhot, lds.end(), 0x7FBADBADu);  // poison (a NaN pattern)
     const cxk::Tile<EW> t{lds.data() + sc.nhot, lds.data(), lds.data() + sc.nhot + (size_t)c.L.S * EW};

@@ -85,13 +85,12 @@ int run_blocks_l1(const cxk::KArgs& a) {
 }  // namespace
 
 // emu_step_ex through the step program with the level-1 key ring (4 envs per
-// wave, the analytic program: where the library launches the form)
+// wave, the analytic program, more than one key window, the fused scan)
 extern "C" int emu_step_keyl1(void* scene, float* dyn, uint32_t* keys, uint32_t* err, const float* geom, int gstride,
                               int B, int n_steps, float dt, int stages, const float* action, int action_body,
                               const float* dyn_reset, uint32_t* resets, int32_t* chosen, int32_t* cells) {
   EmuScene* s = static_cast<EmuScene*>(scene);
-  if (cxk::launch_fnset(s->fnset, 0) != cxk::FNS_ANALYTIC || n_steps <= cxk::KWIN ||
-      !cxk::scan_fused<4>(cxk::make_ctx<4>(s->s)))
+  if (!cxl::key_helper_may_run(s->fnset, 4, n_steps) || !cxk::scan_fused<4>(cxk::make_ctx<4>(s->s)))
     return g_err = "not a launch of the level-1 key form", -1;
   cxk::KArgs a{};
   a.sc = &s->s;

@@ -5,7 +5,7 @@
 CXX ?= g++
 FLAGS = -DCOTIX_EMU_POISON -std=c++17 -ffp-contract=off -fno-fast-math -Wall -Wno-unused-function -Wno-unknown-pragmas
 CS = ../../parallax_amd/csrc
-DEPS = cotix_emu_keyl1.cpp cotix_emu.cpp cotix_simt.h $(CS)/cotix_kernel.h $(CS)/cotix_device.h $(CS)/cotix_scene.h \
+DEPS = cotix_emu_keyl1.cpp cotix_emu.cpp cotix_simt.h $(CS)/cotix_kernel.h $(CS)/cotix_plan.h $(CS)/cotix_device.h $(CS)/cotix_scene.h \
 	$(CS)/cotix_grad.h $(CS)/cotix_body.h $(CS)/cotix_spec_hdrs.h
 
 all: build/libcotix_emu_keyl1.so build/keyl1_asan_driver
