@@ -425,6 +425,51 @@ int cotix_rollout_backward_ex2(cotix_scene* scene, const float* saved_dyn, const
                                int stages, const float* action, int action_body, const float* ret_weights,
                                float* grad_action, float* grad_dyn0, float* grad_params, cotix_stream_t stream);
 
+/* Differentiable eval: the gradient of cotix_eval's reward with respect to
+ * the 26 parameters of the affine control and to the entry state, through the
+ * closed-loop control, the judge's piecewise-linear rate, the end reward and
+ * the per-env episode end (jax.grad of AbstractEnvironment.eval,
+ * cotix/_envs.py:37-132: the executed branch of every lax.cond, collider
+ * choices fixed, balanced ties of max / min / clip; region membership, region
+ * rewards, biases and clip bounds are constants).  One launch each.
+ *
+ * cotix_eval_rollout: cotix_eval with reset_mode 0 that also saves what the
+ * backward needs.  dyn, keys, err, reward and finished come out bit-identical
+ * to cotix_eval's on the same inputs.
+ *   judge      required; control nullable (then no control acts)
+ *   action     must be NULL (a held action is not differentiated); action_body ignored
+ *   saved_dyn  device f32, saved_keys device u32, tape device u32: the
+ *              layouts of cotix_rollout_ex with n_steps = n_nfe * wfe; the
+ *              tape is required
+ *   judge_rec  device u32 [n_steps + 1][B]: per env and state index t (0: the
+ *              entry state, t: the state after env-step t), with t* the first
+ *              t at which is_done holds: bit 0 t < t* (env-step t + 1 counts;
+ *              bits 3.. then 1 + the rate region holding the state, 0 none),
+ *              bit 1 t == t*, bit 2 the env was finished at entry (alone, at
+ *              every t), 0 for t > t*
+ * cotix_eval_backward: from those arrays and the same judge, control, sizes,
+ * dt, stages and geometry.  Outputs (each nullable, every word of the batch
+ * written, the env index last as in grad_dyn0):
+ *   grad_control f32 [26][B]: rows 6 i + q = d reward / d gain[i][q], rows
+ *              12 + 6 i + q = d / d target[i][q], rows 24 + i = d / d bias[i]
+ *              (zero gains and biases included); needs control
+ *   grad_dyn0  f32 [n_bodies][6][B]: d reward / d the entry state
+ *   grad_dv    f32 [n_steps][B][2]: d reward / d the control's impulse of each
+ *              env-step
+ * An env finished at entry, and every env-step after an env's t*, contribute
+ * exact zeros.  action and grad_params must be NULL (not offered).  The scene
+ * restrictions are cotix_rollout_backward_ex2's. */
+int cotix_eval_rollout(cotix_scene* scene, float* dyn, uint32_t* keys, uint32_t* err, const float* geom,
+                       int geom_stride, int B, int n_nfe, int wfe, float dt, int stages, const cotix_judge* judge,
+                       const cotix_control* control, const float* action, int action_body, float* reward,
+                       uint32_t* finished, float* saved_dyn, uint32_t* saved_keys, uint32_t* tape,
+                       uint32_t* judge_rec, cotix_stream_t stream);
+int cotix_eval_backward(cotix_scene* scene, const float* saved_dyn, const uint32_t* saved_keys, const uint32_t* tape,
+                        const uint32_t* judge_rec, const float* geom, int geom_stride, int B, int n_nfe, int wfe,
+                        float dt, int stages, const cotix_judge* judge, const cotix_control* control,
+                        const float* action, float* grad_control, float* grad_dyn0, float* grad_dv,
+                        float* grad_params, cotix_stream_t stream);
+
 /* Body-level operators (UniversalShape, cotix/_universal_shape.py:87-132), per env:
  * cotix_body_penetration: collides_with (GJK over every part pair of the two
  *   bodies, first colliding pair kept, :87-107) and penetrates_with /

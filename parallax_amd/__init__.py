@@ -10,6 +10,7 @@ from .bodies import AnyBody, BodyView  # noqa: F401
 from .env import BatchedEnv, StepResult  # noqa: F401
 from .envs import (AbstractEnvironment, AffineControl, LinearJudge, PhysicsWorld, VelocityImpulse,  # noqa: F401
                    WorldState)
+from .eval_grad import differentiable_eval, eval_backward, eval_forward  # noqa: F401
 from .params import Params  # noqa: F401
 from .physics import (ContactInfo, ExplicitEulerPhysics, RandomizedCollider, SimpleConstraintSolver,  # noqa: F401
                       check_for_collision_convex, compute_penetration_vector_convex, contact_funcs,

@@ -66,6 +66,10 @@ SIGNATURES = {
     "cotix_rollout_ex": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _F, _I, _P, _I, _P, _P, _P, _P, _P, _P]),
     "cotix_rollout_backward_ex": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _F, _I, _P, _I, _P, _P, _P, _P]),
     "cotix_rollout_backward_ex2": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _F, _I, _P, _I, _P, _P, _P, _P, _P]),
+    "cotix_eval_rollout": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _I, ctypes.POINTER(CotixJudge),
+                                ctypes.POINTER(CotixControl), _P, _I, _P, _P, _P, _P, _P, _P, _P]),
+    "cotix_eval_backward": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _I, ctypes.POINTER(CotixJudge),
+                                 ctypes.POINTER(CotixControl), _P, _P, _P, _P, _P, _P]),
     "cotix_body_penetration": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
     "cotix_body_aabb": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P]),
     "cotix_physics_euler": (_I, [_P, _I, _I, _F, _P]),
@@ -98,7 +102,7 @@ SIGNATURES = {
 
 # entry points an older build given as COTIX_AMD_LIB (bench.py --lib, A/B
 # measurements against a parent commit) may lack; this tree's build has them
-OPTIONAL = {"cotix_scene_last_step_form"}
+OPTIONAL = {"cotix_scene_last_step_form", "cotix_eval_rollout", "cotix_eval_backward"}
 
 
 def _load():

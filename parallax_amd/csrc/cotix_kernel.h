@@ -262,6 +262,36 @@ struct KArgs {
   // of every body, summed over the steps, or null (cotix_rollout_backward_ex2;
   // the GP programs below)
   float* grad_params;
+  // differentiable eval (cotix_eval_rollout / cotix_eval_backward; the ESAVE /
+  // EV programs below): the judge record [n_steps + 1][B] (JREC_*), written by
+  // the forward and read by the backward; d reward / d the affine control's
+  // 26 parameters [26][B] (CtlGrad), or null.  grad_action is then
+  // d reward / d dv_t [n_steps][B][2], grad_dyn d reward / d the entry state
+  uint32_t* judge_rec;
+  float* grad_control;
+};
+
+// The judge record of the differentiable eval: one word per env and state
+// index t = 0 .. n_steps (s_0 the entry state, s_t the state after env-step t;
+// word t of env g at judge_rec[t * B + g]).  With t* the first t at which
+// is_done(s_t) holds:
+//   JREC_LIVE  t < t*: env-step t + 1 is on the reward's chain; bits 3.. then
+//              hold 1 + the rate region holding s_t (0: none; t >= 1)
+//   JREC_END   t == t*: the end reward is taken at s_t
+//   JREC_FIN0  the env was finished at entry: its reward is the carry's, no
+//              state enters it (set at every t, alone)
+//   0          t > t*: the forward's saved rows of such a step are not on the
+//              chain (a done env is stepped on to the NFE's end, restored, and
+//              stepped again from the premature-out state in later NFEs)
+// The backward reads nothing else about the episode: it never evaluates the
+// judge's regions or the error bits on a restored state.
+constexpr uint32_t JREC_LIVE = 1u, JREC_END = 2u, JREC_FIN0 = 4u;
+constexpr int JREC_REGION_SHIFT = 3;
+// d reward / d (gain[2][6], target[2][6], bias[2]) of cotix_control, in that
+// order, summed over the env's live steps in its owning lane's registers
+constexpr int CTL_NPAR = 26;
+struct CtlGrad {
+  float v[CTL_NPAR];
 };
 
 // The rollout's saved rows (save_dyn: nb*6 state words per env-step; tape:
@@ -470,11 +500,12 @@ CX_DEV void lunar_constraints(cx::Dyn& lander, cx::Dyn& rleg, cx::Dyn& lleg, con
 enum : int { FNS_ANALYTIC = 1, FNS_CONVEX = 2, FNS_CIRCLE_POLY = 4, FNS_AABB_POLY = 8 };
 // the FNSET instantiation of the step kernel for a scene's function set
 // (launcher and host emulation): analytic scenes get the analytic program,
-// modes 1 (rollout), 2 / 4 (its backward: re-play / tape) and 3 (eval with a
-// judge or control) the full one
+// modes 1 (rollout), 2 / 4 (its backward: re-play / tape), 3 (eval with a
+// judge or control) and 5 / 6 (the differentiable eval, forward / backward)
+// the full one
 CX_HD int launch_fnset(int fs, int mode) {
   if ((fs & ~FNS_ANALYTIC) == 0) return FNS_ANALYTIC;
-  if (mode >= 1 && mode <= 4) return FNS_ANALYTIC | FNS_CONVEX | FNS_CIRCLE_POLY | FNS_AABB_POLY;
+  if (mode >= 1 && mode <= 6) return FNS_ANALYTIC | FNS_CONVEX | FNS_CIRCLE_POLY | FNS_AABB_POLY;
   if ((fs & ~(FNS_ANALYTIC | FNS_CONVEX)) == 0) return FNS_ANALYTIC | FNS_CONVEX;
   if ((fs & FNS_CIRCLE_POLY) == 0) return FNS_ANALYTIC | FNS_CONVEX | FNS_AABB_POLY;
   return FNS_ANALYTIC | FNS_CONVEX | FNS_CIRCLE_POLY | FNS_AABB_POLY;
@@ -3226,6 +3257,30 @@ CX_DEV void ph_JE(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, int lane) 
     t.w(L.jfin, e) = al ? 1u : 0u;
   }
 }
+// the differentiable eval's judge record of state index ti (JREC_*), on the
+// env's lane right after ph_JB (ti == 0, the launch's entry) or ph_J (ti =
+// step + 1), from the words they leave: jal (t* <= ti) and jsn (t* == ti).
+// fin0: the env's finished flag at entry, kept in the lane's register
+template <int EW>
+CX_DEV void ph_jrec(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, int lane, int ti, uint32_t& fin0) {
+  const Lay& L = c.L;
+  const JudgeArgs& j = a.judge;
+  for (int e = lane; e < EW; e += WAVE) {
+    const int g = env0 + e;
+    if (g >= a.B) continue;
+    if (ti == 0) fin0 = t.w(L.jfin, e);
+    uint32_t rec;
+    if (fin0 != 0u) {
+      rec = JREC_FIN0;
+    } else if (t.w(L.jal, e) == 0u) {
+      const int r = (ti > 0 && j.nrr > 0) ? first_box<EW>(t, L.dyn, e, j.nrr, j.prbody, j.prlo, j.prhi) : -1;
+      rec = JREC_LIVE | ((uint32_t)(r + 1) << JREC_REGION_SHIFT);
+    } else {
+      rec = (ti == 0 || t.w(L.jsn, e) != 0u) ? JREC_END : 0u;
+    }
+    a.judge_rec[(size_t)ti * a.B + g] = rec;
+  }
+}
 
 // all ones where env e's restart is taken at the store (rs and its flag),
 // else 0: a mask on the word offset, not a select between the layout's
@@ -3438,6 +3493,90 @@ CX_DEV void grad_action_flush(const KArgs& a, int env0, int lane, int EWn, GradO
     a.grad_action[2 * ((size_t)go.step * a.B + g) + 1] = go.y;
   }
   go.step = -1;
+}
+
+// ---------------------------------------------------------------------------
+// The differentiable eval's backward (EV forms of run_wave_backward_tape, phase
+// G).  The judge words of the tile (jfin ..) are free in a backward: the step's
+// judge record of each env and the control body's state before the step are
+// kept there, and the restart-state words hold the step's seed
+// d reward / d s_step (direct part), staged per env from the record.
+// ---------------------------------------------------------------------------
+CX_DEV int ev_state_word(const Ctx& c) { return c.L.jfin; }     // 6 words: s_step[control body]
+CX_DEV int ev_rec_word(const Ctx& c) { return c.L.jfin + 6; }  // the judge record of s_step
+// the seed of state index `ti` into the tile words at dst, item = (word, env):
+// end_w where the episode ends at s_ti; dt * (rate_w + the rate region's
+// weights) where the env is live there and ti >= 1; else 0.  The weights are
+// the judge's compacted (word, w) terms, matched by word (uniform loops over
+// the kernel arguments)
+template <int EW>
+CX_DEV void ev_stage_seed(const KArgs& a, const Ctx& c, Tile<EW> t, int lane, int ti, int dst) {
+  const JudgeArgs& j = a.judge;
+  for (int w = lane; w < c.nb * 6 * EW; w += WAVE) {
+    const int e = w % EW, off = w / EW;
+    const uint32_t rec = t.w(ev_rec_word(c), e);
+    const bool end = (rec & JREC_END) != 0u, live = (rec & JREC_LIVE) != 0u && ti > 0;
+    const int r = (int)(rec >> JREC_REGION_SHIFT) - 1;
+    float v = 0.0f;
+    for (int q = 0; q < j.nend; ++q) v = (end && (int)j.end_k[q] == off) ? j.end_w[q] : v;
+    for (int q = 0; q < j.nrate; ++q) v = (live && (int)j.rate_k[q] == off) ? j.rate_w[q] * a.dt : v;
+    for (int q = 0; q < j.nrr; ++q)
+      for (int m = 0; m < j.npr[q]; ++m) v = (live && q == r && (int)j.pr_k[q][m] == off) ? v + j.pr_w[q][m] * a.dt : v;
+    t.f(dst + off, e) = v;
+  }
+}
+// the derivative of jnp.clip(x, lo, hi) = min(hi, max(lo, x)) in x, balanced
+// ties: one half on a bound, a NaN passes (the reference's maximum / minimum)
+CX_DEV float clip_slope(float x, float lo, float hi) {
+  const float m1 = lo > x ? 0.0f : (lo == x ? 0.5f : 1.0f);
+  const float y = lo > x ? lo : x;  // max(lo, x), NaN kept
+  const float m2 = hi < y ? 0.0f : (hi == y ? 0.5f : 1.0f);
+  return m1 * m2;
+}
+// the control's part of one reverse step on the env's lane: (gx, gy) =
+// d reward / d dv of the step; cq[q] = sum_i m_i g_i gain[i][q], which the
+// caller subtracts from the control body's pre-step adjoint; the 26 parameter
+// sums.  The unclipped value is control_dv's own sum on the state it read
+template <int EW>
+CX_DEV void ctl_vjp(const KArgs& a, const Ctx& c, Tile<EW> t, int e, float gx, float gy, float (&cq)[6], CtlGrad& cg) {
+  float s[6];
+#pragma unroll
+  for (int q = 0; q < 6; ++q) {
+    s[q] = t.f(ev_state_word(c) + q, e);
+    cq[q] = 0.0f;
+  }
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    float acc = 0.0f;
+    bool any = false;
+#pragma unroll
+    for (int q = 0; q < 6; ++q)
+      if (a.ctl.gain[i][q] != 0.0f) {
+        const float term = a.ctl.gain[i][q] * (a.ctl.target[i][q] - s[q]);
+        acc = any ? acc + term : term;
+        any = true;
+      }
+    if (a.ctl.bias[i] != 0.0f) acc = any ? acc + a.ctl.bias[i] : a.ctl.bias[i];
+    const float m = a.ctl.sat ? clip_slope(acc, a.ctl.lo[i], a.ctl.hi[i]) : 1.0f;
+    const float mg = m * (i == 0 ? gx : gy);
+#pragma unroll
+    for (int q = 0; q < 6; ++q) {
+      cq[q] = cq[q] + mg * a.ctl.gain[i][q];
+      cg.v[6 * i + q] = cg.v[6 * i + q] + mg * (a.ctl.target[i][q] - s[q]);
+      cg.v[12 + 6 * i + q] = cg.v[12 + 6 * i + q] + mg * a.ctl.gain[i][q];
+    }
+    cg.v[24 + i] = cg.v[24 + i] + mg;
+  }
+}
+// an env whose step is not on the chain (not JREC_LIVE): its adjoint becomes
+// the state's own seed (end_w at the episode's end, else zeros) and its
+// d reward / d dv is zero; nothing is pushed through the step's VJPs
+template <int EW>
+CX_DEV bool ev_skip(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, int e, int step, GradOut* go) {
+  if ((t.w(ev_rec_word(c), e) & JREC_LIVE) != 0u) return false;
+  for (int k = 0; k < c.nb * 6; ++k) t.f(c.L.adj + k, e) = t.f(c.L.rst + k, e);
+  if (a.grad_action != nullptr) grad_action_out(a, env0 + e, step, 0.0f, 0.0f, go);
+  return true;
 }
 
 // phase G: reverse of one step (one lane per env).  Entry: adj = d ret /
@@ -3693,9 +3832,11 @@ CX_DEV void ph_GE(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, int lane) 
 // the chain's own loops (g_regs: the one-wave form's schedule, the adjoints
 // live only across one step); otherwise the caller's registers carry them
 // GP: the body parameters' gradient too (gpar_resolution)
-template <int EW, int NB, bool TILE = false, bool GP = false>
+// EV: the differentiable eval's step (the control's VJP, ctl_vjp; the seed
+// of every step, staged per env)
+template <int EW, int NB, bool TILE = false, bool GP = false, bool EV = false>
 CX_DEV void g_chain(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, int e, int step, float (&g)[NB][6],
-                    GradOut* go = nullptr) {
+                    GradOut* go = nullptr, CtlGrad* cg = nullptr) {
   using namespace cx;
   const SceneHdr& sc = c.sh;
   const Lay& L = c.L;
@@ -3790,6 +3931,18 @@ CX_DEV void g_chain(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, int e, i
       }
     grad_action_out(a, g_env, step, gx, gy, go);
   }
+  float evx = 0.0f, evy = 0.0f;  // (EV) d reward / d dv: v[control body] += dv after Euler
+  if (EV && a.ctl.on) {
+#pragma unroll
+    for (int b = 0; b < NB; ++b)
+      if (b == a.ctl.body) {
+        evx = g[b][2];
+        evy = g[b][3];
+      }
+  }
+  if (EV && a.grad_action != nullptr) grad_action_out(a, g_env, step, evx, evy, go);
+  float cq[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+  if (EV && a.ctl.on) ctl_vjp<EW>(a, c, t, e, evx, evy, cq, *cg);
 #pragma unroll
   for (int b = 0; b < NB; ++b) {
     if (a.stages & COTIX_STAGE_EULER) {  // p += v dt, angle += w dt
@@ -3797,22 +3950,27 @@ CX_DEV void g_chain(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, int e, i
       g[b][3] = g[b][3] + g[b][1] * a.dt;
       g[b][5] = g[b][5] + g[b][4] * a.dt;
     }
-    if (step > 0)
+    if (EV || step > 0)
 #pragma unroll
-      for (int k = 0; k < 6; ++k) g[b][k] = g[b][k] + t.f(L.rst + 6 * b + k, e);  // ret_w (staged)
+      for (int k = 0; k < 6; ++k) g[b][k] = g[b][k] + t.f(L.rst + 6 * b + k, e);  // ret_w / the step's seed (staged)
+    if (EV && a.ctl.on && b == a.ctl.body)
+#pragma unroll
+      for (int k = 0; k < 6; ++k) g[b][k] = g[b][k] - cq[k];  // dv reads the state before the step
     if (TILE)
 #pragma unroll
       for (int k = 0; k < 6; ++k) t.f(L.adj + 6 * b + k, e) = g[b][k];
   }
 }
-template <int EW, int NB, bool GP = false>
-CX_DEV void g_regs(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, int e, int step, GradOut* go = nullptr) {
+template <int EW, int NB, bool GP = false, bool EV = false>
+CX_DEV void g_regs(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, int e, int step, GradOut* go = nullptr,
+                   CtlGrad* cg = nullptr) {
   float g[NB][6];
-  g_chain<EW, NB, true, GP>(a, c, t, env0, e, step, g, go);
+  g_chain<EW, NB, true, GP, EV>(a, c, t, env0, e, step, g, go, cg);
 }
 
-template <int EW, int FNSET = FNS_ANALYTIC, bool GP = false>
-CX_DEV void ph_G(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, int lane, int step, GradOut* go = nullptr) {
+template <int EW, int FNSET = FNS_ANALYTIC, bool GP = false, bool EV = false>
+CX_DEV void ph_G(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, int lane, int step, GradOut* go = nullptr,
+                 CtlGrad* cg = nullptr) {
   using namespace cx;
   const SceneHdr& sc = c.sh;
   const int nb = c.nb;
@@ -3820,13 +3978,14 @@ CX_DEV void ph_G(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, int lane, i
   for (int e = lane; e < EW; e += WAVE) {
     const int g = env0 + e;
     if (g >= a.B) continue;
+    if (EV && ev_skip<EW>(a, c, t, env0, e, step, go)) continue;
 #ifndef COTIX_NO_GREGS  // (tooling: the tile form for every scene, tests/test_grad_cpu.py checks the two agree)
     if (FNSET == FNS_ANALYTIC && nb == 5) {  // RoboCup
-      g_regs<EW, 5, GP>(a, c, t, env0, e, step, go);
+      g_regs<EW, 5, GP, EV>(a, c, t, env0, e, step, go, cg);
       continue;
     }
     if (FNSET == FNS_ANALYTIC && nb == 7) {  // the box world
-      g_regs<EW, 7, GP>(a, c, t, env0, e, step, go);
+      g_regs<EW, 7, GP, EV>(a, c, t, env0, e, step, go, cg);
       continue;
     }
 #endif
@@ -3956,6 +4115,14 @@ CX_DEV void ph_G(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, int lane, i
       const int o = L.adj + 6 * a.action_body;
       grad_action_out(a, g, step, t.f(o + 2, e), t.f(o + 3, e), go);
     }
+    float evx = 0.0f, evy = 0.0f;  // (EV) d reward / d dv: v[control body] += dv after Euler
+    if (EV && a.ctl.on) {
+      evx = t.f(L.adj + 6 * a.ctl.body + 2, e);
+      evy = t.f(L.adj + 6 * a.ctl.body + 3, e);
+    }
+    if (EV && a.grad_action != nullptr) grad_action_out(a, g, step, evx, evy, go);
+    float cq[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    if (EV && a.ctl.on) ctl_vjp<EW>(a, c, t, e, evx, evy, cq, *cg);
     for (int b = 0; b < nb; ++b) {
       const int o = L.adj + 6 * b;
       if (a.stages & COTIX_STAGE_EULER) {  // p += v dt, angle += w dt
@@ -3963,8 +4130,11 @@ CX_DEV void ph_G(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, int lane, i
         t.f(o + 3, e) = t.f(o + 3, e) + t.f(o + 1, e) * a.dt;
         t.f(o + 5, e) = t.f(o + 5, e) + t.f(o + 4, e) * a.dt;
       }
-      if (step > 0)
-        for (int k = 0; k < 6; ++k) t.f(o + k, e) = t.f(o + k, e) + t.f(L.rst + 6 * b + k, e);  // ret_w (staged)
+      if (EV || step > 0)
+        for (int k = 0; k < 6; ++k)
+          t.f(o + k, e) = t.f(o + k, e) + t.f(L.rst + 6 * b + k, e);  // ret_w / the step's seed (staged)
+      if (EV && a.ctl.on && b == a.ctl.body)
+        for (int k = 0; k < 6; ++k) t.f(o + k, e) = t.f(o + k, e) - cq[k];  // dv reads the state before the step
     }
   }
 }
@@ -4307,11 +4477,20 @@ CX_DEV void key_l1_next(const KArgs& a, const Ctx& c, KeyL1<EW>& h, const R& run
   h.s0 += KL1R;
 }
 
-template <int EW, int FNSET, bool ROLL, bool EVAL = false, bool SDEFER = false, class R = void, class H = NoKeyHelp>
+// ESAVE: the differentiable eval's forward (cotix_eval_rollout) -- the EVAL
+// program that also saves what the rollout forward saves (the state and key
+// before every step, the tape) and writes the judge record (ph_jrec); it has
+// no action and no return, so the rollout's action window and return terms
+// never claim the restart-state words its premature-out state lives in
+template <int EW, int FNSET, bool ROLL, bool EVAL = false, bool SDEFER = false, bool ESAVE = false, class R = void,
+          class H = NoKeyHelp>
 CX_DEV void run_wave(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, const R& run, bool loaded = false,
                      const H& help = H{}) {
   static_assert(!(ROLL && EVAL), "the rollout has no judge");
+  static_assert(!ESAVE || (EVAL && !ROLL && !SDEFER), "the saving eval is the eval program");
   static_assert(!(H::on && (ROLL || EVAL)), "the key helper runs the step program only");
+  constexpr bool SAVE = ROLL || ESAVE;  // the saves and the tape
+  uint32_t fin0 = 0u;                   // (ESAVE) this lane's env was finished at entry
   if (!loaded) run(PH_LOAD, [&](int l) { ph_load_fwd<EW, ROLL, EVAL>(a, c, t, env0, l); });
   const bool keys = keys_on(a);
   // the level-1 key ring (a help policy's `l1`): the keys of a step's slot
@@ -4319,7 +4498,10 @@ CX_DEV void run_wave(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, const R
   static_assert(!L1 || H::on, "the level-1 key ring is the key helper's");
   const int nk1 = L1 ? key_l1_keys(c.sh, t.tb) : 0, ko1 = L1 && c.nt > 0 ? t.ti(c.sh.o_tn2) : 0;
   if (EVAL && a.judge.on) {  // the first NFE's start
-    run(PH_J, [&](int l) { ph_JB<EW>(a, c, t, env0, l); });
+    run(PH_J, [&](int l) {
+      ph_JB<EW>(a, c, t, env0, l);
+      if (ESAVE) ph_jrec<EW>(a, c, t, env0, l, 0, fin0);
+    });
     run(PH_J, [&](int l) { ph_JS<EW>(c, t, l); });
   }
 
@@ -4369,7 +4551,7 @@ CX_DEV void run_wave(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, const R
     // (the window's reads before this step's save stores: they wait only for
     // the previous step's, long complete)
     if (awin && step % AWIN == 0) run(PH_K, [&](int l) { act_window_fill<EW>(a, c, t, env0, l, step); });
-    if (ROLL) run(PH_SAVE, [&](int l) { ph_save<EW, FNSET == FNS_ANALYTIC>(a, c, t, env0, l, step); });
+    if (SAVE) run(PH_SAVE, [&](int l) { ph_save<EW, FNSET == FNS_ANALYTIC>(a, c, t, env0, l, step); });
     const int slot = step % KWIN;
     if (H::on && keys && slot == 0 && step > 0) {
       help.bar();  // the helper's window (key_helper_next)
@@ -4402,7 +4584,7 @@ CX_DEV void run_wave(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, const R
       if (a.stages & COTIX_STAGE_COLLIDER) run(PH_B, [&](int l) { ph_B_const<EW>(a, c, t, env0, l, bc); });
       if (l1bar) help.bar();
       if (a.stages & COTIX_STAGE_COLLIDER)
-        collider_phases<EW, FNSET, true, R, true, ROLL, L1>(a, c, t, env0, run, slot, kso, mc, step, kl1, ko1);
+        collider_phases<EW, FNSET, true, R, true, SAVE, L1>(a, c, t, env0, run, slot, kso, mc, step, kl1, ko1);
     } else if (FNSET == FNS_ANALYTIC && c.nc * EW <= ABQ * WAVE) {
       // stage 1 reads the pre-Euler state: every read is issued before phase
       // A's writes (stage 2); stage 3 computes the contacts
@@ -4414,7 +4596,7 @@ CX_DEV void run_wave(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, const R
           },
           [&](int l, const ABRegs& r) { ab_contacts<EW>(a, c, t, env0, l, r); });
       if (l1bar) help.bar();
-      if (a.stages & COTIX_STAGE_COLLIDER) collider_phases<EW, FNSET, true, R, FNSET == FNS_ANALYTIC, ROLL, L1>(
+      if (a.stages & COTIX_STAGE_COLLIDER) collider_phases<EW, FNSET, true, R, FNSET == FNS_ANALYTIC, SAVE, L1>(
           a, c, t, env0, run, slot, kso, mc, step, kl1, ko1);
     } else {
       run(PH_A, [&](int l) {
@@ -4423,12 +4605,12 @@ CX_DEV void run_wave(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, const R
       });
       if (l1bar) help.bar();
       if (a.stages & COTIX_STAGE_COLLIDER)
-        collider_phases<EW, FNSET, true, R, false, ROLL, L1>(a, c, t, env0, run, slot, kso, mc, step, kl1, ko1);
+        collider_phases<EW, FNSET, true, R, false, SAVE, L1>(a, c, t, env0, run, slot, kso, mc, step, kl1, ko1);
     }
     if (a.trace_chosen != nullptr || a.trace_cells != nullptr)
       run(PH_TRACE, [&](int l) { ph_trace<EW>(a, c, t, env0, l, step); });
     if (!CXK_SKIP(a, 32)) {
-      if (ROLL && FNSET == FNS_ANALYTIC && a.tape != nullptr && tape_rec(c.sh) && (a.stages & COTIX_STAGE_COLLIDER))
+      if (SAVE && FNSET == FNS_ANALYTIC && a.tape != nullptr && tape_rec(c.sh) && (a.stages & COTIX_STAGE_COLLIDER))
         run(PH_E1, [&](int l) { ph_E<EW, false, ROLL, true>(a, c, t, env0, l, kso, &rr); });
       else
         run(PH_E1, [&](int l) { ph_E<EW, false, ROLL>(a, c, t, env0, l, kso, &rr); });
@@ -4441,7 +4623,10 @@ CX_DEV void run_wave(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, const R
       });
     }
     if (EVAL && a.judge.on) {  // cotix_eval: NFE bookkeeping (cotix/_envs.py:77-117)
-      run(PH_J, [&](int l) { ph_J<EW>(a, c, t, env0, l); });
+      run(PH_J, [&](int l) {
+        ph_J<EW>(a, c, t, env0, l);
+        if (ESAVE) ph_jrec<EW>(a, c, t, env0, l, step + 1, fin0);
+      });
       run(PH_J, [&](int l) { ph_JS<EW>(c, t, l); });
       if ((step + 1) % a.nfe_len == 0) {
         run(PH_J, [&](int l) { ph_JE<EW>(a, c, t, env0, l); });
@@ -4452,7 +4637,7 @@ CX_DEV void run_wave(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, const R
       }
     }
   }
-  if (ROLL && a.tape != nullptr && (a.stages & COTIX_STAGE_COLLIDER) && a.n_steps > 0)
+  if (SAVE && a.tape != nullptr && (a.stages & COTIX_STAGE_COLLIDER) && a.n_steps > 0)
     run(PH_SAVE, [&](int l) { tape_save<EW, FNSET == FNS_ANALYTIC>(a, c, t, env0, l, a.n_steps - 1); });  // the last step's
   if (defer && a.n_steps > 0 && !rstore) run(PH_R, [&](int l) { ph_R<EW>(c, t, l); });  // the last step's
   run(PH_STORE, [&](int l) { ph_store<EW, ROLL, EVAL>(a, c, t, env0, l, rstore); });
@@ -4465,16 +4650,38 @@ CX_DEV void run_wave(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, const R
 // No key split, narrowphase, RNG scan or choice runs: the tape holds their
 // outcome, and every value the VJPs read is bit-identical to the re-play's
 // GP: with the body parameters' gradient (KArgs::grad_params, zeroed here)
-template <int EW, int FNSET, bool GP = false, class R>
+// EV: the differentiable eval's backward (cotix_eval_backward): the forward
+// is the saving eval (run_wave ESAVE).  Each step re-applies the device
+// control on the restored state (euler_item EVAL: control_dv's own bits),
+// stages its per-env seed from the judge record (ev_stage_seed; the record is
+// read one step ahead with the saved rows, behind the gradient stores) and
+// skips the envs whose step is not on the chain (ev_skip); the adjoint starts
+// from the last state's seed.  d reward / d dv goes out through grad_action,
+// the control's 26 parameter sums stay in the env lane's registers (CtlGrad)
+// until the end
+template <int EW, int FNSET, bool GP = false, bool EV = false, class R>
 CX_DEV void run_wave_backward_tape(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, const R& run) {
+  static_assert(!(GP && EV), "the eval backward does not carry the body parameters' gradient");
+  CtlGrad cg;
+  auto jrec_read = [&](int l, int ti) -> uint32_t {  // the judge record of s_ti on the env's lane
+    const int g = env0 + l;
+    return (l < EW && g < a.B) ? a.judge_rec[(size_t)ti * a.B + g] : 0u;
+  };
   run(PH_ADJ, [&](int l) {
     if (GP) gpar_zero<EW>(a, c, env0, l);
     ws_poly_init<EW>(c, t, l);
     ph_geo<EW>(a, c, t, env0, l);
-    ph_adj_init<EW>(a, c, t, env0, l);
-    stage_ret_w<EW>(a, c, t, l);
+    if (EV) {
+#pragma unroll
+      for (int k = 0; k < CTL_NPAR; ++k) cg.v[k] = 0.0f;
+      if (l < EW) t.w(ev_rec_word(c), l) = jrec_read(l, a.n_steps);
+    } else {
+      ph_adj_init<EW>(a, c, t, env0, l);
+      stage_ret_w<EW>(a, c, t, l);
+    }
     for (int e = l; e < EW; e += WAVE) t.w(c.L.pcv, e) = 0u;  // phase T's pose entries
   });
+  if (EV) run(PH_ADJ, [&](int l) { ev_stage_seed<EW>(a, c, t, l, a.n_steps, c.L.adj); });  // d reward / d s_T
   const bool col = (a.stages & COTIX_STAGE_COLLIDER) != 0;
   const bool edges = FNSET != FNS_ANALYTIC && c.sh.poly && ge_fits(c) && ge_edges_fit(c);
   constexpr bool TR = FNSET == FNS_ANALYTIC;  // the tape's resolution records (tape_rec)
@@ -4485,10 +4692,16 @@ CX_DEV void run_wave_backward_tape(const KArgs& a, const Ctx& c, Tile<EW> t, int
   // the reverse chain (the same for both restore forms)
   auto reverse_step = [&](int step, auto dphase) CXK_INLINE_LAMBDA {
     run(PH_A, [&](int l) {  // Euler (+ gravity, + action); no key split, no collider scratch
+      if (EV) ev_stage_seed<EW>(a, c, t, l, step, c.L.rst);  // (the record: the restore phase's)
       if (a.stages & (COTIX_STAGE_EULER | COTIX_STAGE_GRAVITY))
         for (int w = l; w < c.nb * EW; w += WAVE) {
           const int e = w % EW, b = w / EW;
-          if (env0 + e < a.B) euler_item<EW>(a, c, t, env0, e, b, step, apf, ac);
+          if (env0 + e >= a.B) continue;
+          if (EV && a.ctl.on && b == a.ctl.body) {  // the state the control reads, for its VJP
+#pragma unroll
+            for (int q = 0; q < 6; ++q) t.f(ev_state_word(c) + q, e) = t.f(c.L.dyn + 6 * b + q, e);
+          }
+          euler_item<EW, EV>(a, c, t, env0, e, b, step, apf, ac);
         }
     });
     if (col) {
@@ -4503,18 +4716,29 @@ CX_DEV void run_wave_backward_tape(const KArgs& a, const Ctx& c, Tile<EW> t, int
       else
         run(PH_GE, [&](int l) { ph_GE<EW>(a, c, t, env0, l); });
     }
-    run(PH_G, [&](int l) { ph_G<EW, FNSET, GP>(a, c, t, env0, l, step, &go); });
+    run(PH_G, [&](int l) { ph_G<EW, FNSET, GP, EV>(a, c, t, env0, l, step, &go, &cg); });
+  };
+  // (EV) the end: the last step's d reward / d dv, the parameter sums, the entry state's adjoint
+  auto finish = [&](int l) CXK_INLINE_LAMBDA {
+    if (a.grad_action != nullptr) grad_action_flush(a, env0, l, EW, go);  // step 0's
+    if (EV && a.grad_control != nullptr && l < EW && env0 + l < a.B) {
+#pragma unroll
+      for (int k = 0; k < CTL_NPAR; ++k) a.grad_control[(size_t)k * a.B + env0 + l] = cg.v[k];
+    }
+    ph_adj_store<EW>(a, c, t, env0, l);
   };
   if (TR && rows_restore<EW>(a, c)) {  // rows, two steps ahead (two register sets: the loop unrolled by two)
     struct Pre {
       RowRegs rw;
       ActRegs an;
+      uint32_t jr = 0u;  // (EV) the step's judge record
     };
     Pre p0, p1;
     const TapeRegs none{};
     auto prefetch = [&](int l, int s, Pre& p) CXK_INLINE_LAMBDA {
       restore_rows_fetch<EW>(a, c, env0, l, s, p.rw);
       if (apf) act_fetch<EW>(a, c, env0, l, s, p.an);
+      if (EV) p.jr = jrec_read(l, s);
     };
     if (a.n_steps > 0)
       run(PH_RESTORE, [&](int l) {
@@ -4525,6 +4749,7 @@ CX_DEV void run_wave_backward_tape(const KArgs& a, const Ctx& c, Tile<EW> t, int
       run(PH_RESTORE, [&](int l) {
         restore_rows_apply<EW>(c, t, l, cur.rw);
         ac = cur.an;
+        if (EV && l < EW) t.w(ev_rec_word(c), l) = cur.jr;
         if (a.grad_action != nullptr) grad_action_flush(a, env0, l, EW, go);  // (stores, then the prefetch reads)
         if (step > 1) prefetch(l, step - 2, cur);
       });
@@ -4534,17 +4759,16 @@ CX_DEV void run_wave_backward_tape(const KArgs& a, const Ctx& c, Tile<EW> t, int
       one(step, p0);
       if (step >= 1) one(step - 1, p1);
     }
-    run(PH_ADJ, [&](int l) {
-      if (a.grad_action != nullptr) grad_action_flush(a, env0, l, EW, go);  // step 0's
-      ph_adj_store<EW>(a, c, t, env0, l);
-    });
+    run(PH_ADJ, finish);
     return;
   }
   RestoreRegs rr;
   TapeRegs tn, tr;  // the next (earlier) step's tape words, the current step's
   ActRegs an;       // the actions, one step ahead as the state
+  uint32_t jn = 0u;  // (EV) the judge record, one step ahead
   if (a.n_steps > 0)
     run(PH_RESTORE, [&](int l) {
+      if (EV) jn = jrec_read(l, a.n_steps - 1);
       restore_fetch<EW>(a, c, env0, l, a.n_steps - 1, rr);
       if (col) tape_fetch<EW, TR>(a, c, env0, l, a.n_steps - 1, tn);
       if (apf) act_fetch<EW>(a, c, env0, l, a.n_steps - 1, an);
@@ -4557,8 +4781,10 @@ CX_DEV void run_wave_backward_tape(const KArgs& a, const Ctx& c, Tile<EW> t, int
         if (edges) tape_edge_fetch<EW>(a, c, env0, l, step, tr);
       }
       ac = an;
+      if (EV && l < EW) t.w(ev_rec_word(c), l) = jn;
       if (a.grad_action != nullptr) grad_action_flush(a, env0, l, EW, go);  // (stores, then the prefetch reads)
       if (step > 0) {  // the next (earlier) step, in flight
+        if (EV) jn = jrec_read(l, step - 1);
         restore_fetch<EW>(a, c, env0, l, step - 1, rr);
         if (col) tape_fetch<EW, TR>(a, c, env0, l, step - 1, tn);
         if (apf && !a.action_held) act_fetch<EW>(a, c, env0, l, step - 1, an);
@@ -4566,10 +4792,7 @@ CX_DEV void run_wave_backward_tape(const KArgs& a, const Ctx& c, Tile<EW> t, int
     });
     reverse_step(step, [&](int l) { ph_D_tape<EW, TR>(a, c, t, env0, l, tr); });
   }
-  run(PH_ADJ, [&](int l) {
-    if (a.grad_action != nullptr) grad_action_flush(a, env0, l, EW, go);  // step 0's
-    ph_adj_store<EW>(a, c, t, env0, l);
-  });
+  run(PH_ADJ, finish);
 }
 
 // ---------------------------------------------------------------------------

@@ -48,7 +48,7 @@ constexpr int EW_ALL = 1 | 2 | 4 | 8;
 constexpr StepKey STEP_KERNELS[] = {
     // generic, every tiling: the step program per contact-function set, the
     // other programs (1 rollout forward, 2 backward re-play, 3 eval with a
-    // judge / control, 4 tape backward) analytic or full
+    // judge / control, 4 tape backward; 5 / 6 below) analytic or full
     {F_AN, 0, cxk::SPEC_GENERIC, false, EW_ALL},
     {F_PP, 0, cxk::SPEC_GENERIC, false, EW_ALL},
     {F_AP, 0, cxk::SPEC_GENERIC, false, EW_ALL},
@@ -66,6 +66,11 @@ constexpr StepKey STEP_KERNELS[] = {
     {F_ALL, 2, cxk::SPEC_GENERIC, true, EW_ALL},
     {F_AN, 4, cxk::SPEC_GENERIC, true, EW_ALL},
     {F_ALL, 4, cxk::SPEC_GENERIC, true, EW_ALL},
+    // the differentiable eval: the eval that also saves (5) and its tape backward (6)
+    {F_AN, 5, cxk::SPEC_GENERIC, false, EW_ALL},
+    {F_ALL, 5, cxk::SPEC_GENERIC, false, EW_ALL},
+    {F_AN, 6, cxk::SPEC_GENERIC, false, EW_ALL},
+    {F_ALL, 6, cxk::SPEC_GENERIC, false, EW_ALL},
     // the reference scenes' step programs at 4 and 2 envs per wave, either PRNG layout
     {F_AN, 0, cxk::SPEC_ROBOCUP, false, 2 | 4},
     {F_AN, 0, cxk::SPEC_ROBOCUP_PART, false, 2 | 4},
@@ -83,6 +88,11 @@ constexpr StepKey STEP_KERNELS[] = {
     // ... and their tape backward with the body parameters' gradient
     {F_AN, 4, cxk::SPEC_ROBOCUP, true, 4},
     {F_AN, 4, cxk::SPEC_BOX, true, 4},
+    // ... and their differentiable eval
+    {F_AN, 5, cxk::SPEC_ROBOCUP, false, 4},
+    {F_AN, 6, cxk::SPEC_ROBOCUP, false, 4},
+    {F_AN, 5, cxk::SPEC_BOX, false, 4},
+    {F_AN, 6, cxk::SPEC_BOX, false, 4},
 };
 // the step program with a key-window helper wave per env group, without and
 // with the level-1 key ring: RoboCup's specialization
@@ -187,7 +197,9 @@ constexpr SplitKey split_key(const LaunchPlan& p) { return {p.nb, p.spec, 0}; }
 
 // sc: the scene's header and tables; fnset: its contact-function mask; a: the
 // launch's arguments (sc / sh are not read); mode 0 step, 1 rollout forward,
-// 2 backward re-play, 3 eval with a judge / control, 4 tape backward
+// 2 backward re-play, 3 eval with a judge / control, 4 tape backward, 5 the
+// eval that also saves, 6 its tape backward (one wave per env group: the
+// split form does not carry the control's gradient)
 inline LaunchPlan plan_launch(const cxk::SceneDev& sc, int fnset, Variant v, const cxk::KArgs& a, int mode,
                               Device dev) {
   LaunchPlan p{};

@@ -622,6 +622,94 @@ int cotix_rollout_backward_ex2(cotix_scene* scene, const float* saved_dyn, const
   return launch(scene, ka, tape ? 4 : 2, stream);
 }
 
+// the scene restrictions of a differentiable launch (cotix_rollout_backward_ex2's)
+static int check_diff_scene(const cotix_scene* scene, int stages) {
+  if ((scene->fnset & cxk::FNS_CIRCLE_POLY) && scene->host.gjk_steps > cx::CP_GJK_MAX)
+    return fail("differentiable eval: circle x polygon gradients record every GJK point: gjk_max_steps <= " +
+                std::to_string(cx::CP_GJK_MAX));
+  if ((stages & COTIX_STAGE_LUNAR) && !(scene->fnset & ~FNS_ANALYTIC))
+    return fail("differentiable eval: the LunarLander joint stage needs the polygon program (a polygon scene)");
+  return 0;
+}
+static int check_eval_sizes(int n_nfe, int wfe) {
+  if (n_nfe < 0 || wfe < 0) return fail("negative size");
+  if (wfe > 0 && n_nfe > INT_MAX / wfe) return fail("n_nfe * wfe overflows");
+  return 0;
+}
+
+int cotix_eval_rollout(cotix_scene* scene, float* dyn, uint32_t* keys, uint32_t* err, const float* geom,
+                       int geom_stride, int B, int n_nfe, int wfe, float dt, int stages, const cotix_judge* judge,
+                       const cotix_control* control, const float* action, int action_body, float* reward,
+                       uint32_t* finished, float* saved_dyn, uint32_t* saved_keys, uint32_t* tape,
+                       uint32_t* judge_rec, cotix_stream_t stream) {
+  if (check_eval_sizes(n_nfe, wfe)) return -1;
+  if (check_step_args(scene, dyn, keys, geom, geom_stride, B, n_nfe * wfe, stages, nullptr, 0)) return -1;
+  (void)action_body;
+  if (action) return fail("differentiable eval: a held action is not differentiated (pass NULL)");
+  if (!judge) return fail("differentiable eval: a judge is required");
+  if (!tape) return fail("differentiable eval: the tape is required (cotix_rollout_tape_words)");
+  if (!err || !reward || !finished || !saved_dyn || !saved_keys || !judge_rec) return fail("null argument");
+  if (check_diff_scene(scene, stages)) return -1;
+  if (B == 0 || n_nfe == 0 || wfe == 0) return 0;
+  cxk::KArgs ka{};
+  const int nb = scene->host.nb;
+  if (cxk::pack_judge(judge, nb * 6, nb, ka.judge, g_err) || cxk::pack_control(control, nb, ka.ctl, g_err)) return -1;
+  ka.dyn = dyn;
+  ka.keys = keys;
+  ka.err = err;
+  ka.geom = geom;
+  ka.gstride = geom_stride;
+  ka.B = B;
+  ka.n_steps = n_nfe * wfe;
+  ka.nfe_len = wfe;
+  ka.dt = dt;
+  ka.stages = stages;
+  ka.reward = reward;
+  ka.finished = finished;
+  ka.save_dyn = saved_dyn;
+  ka.save_keys = saved_keys;
+  ka.tape = tape;
+  ka.tw = cxk::tape_words(nb, scene->host.nc, scene->host.poly);
+  ka.judge_rec = judge_rec;
+  return launch(scene, ka, 5, stream);
+}
+
+int cotix_eval_backward(cotix_scene* scene, const float* saved_dyn, const uint32_t* saved_keys, const uint32_t* tape,
+                        const uint32_t* judge_rec, const float* geom, int geom_stride, int B, int n_nfe, int wfe,
+                        float dt, int stages, const cotix_judge* judge, const cotix_control* control,
+                        const float* action, float* grad_control, float* grad_dyn0, float* grad_dv,
+                        float* grad_params, cotix_stream_t stream) {
+  if (check_eval_sizes(n_nfe, wfe)) return -1;
+  if (check_step_args(scene, saved_dyn, saved_keys, geom, geom_stride, B, n_nfe * wfe, stages, nullptr, 0)) return -1;
+  if (action) return fail("differentiable eval: a held action is not differentiated (pass NULL)");
+  if (grad_params) return fail("differentiable eval: grad_params is not offered (pass NULL)");
+  if (!judge) return fail("differentiable eval: a judge is required");
+  if (!tape) return fail("differentiable eval: the tape is required (the re-play backward does not carry it)");
+  if (!judge_rec) return fail("null argument");
+  if (grad_control && !control) return fail("grad_control needs the control the eval was run with");
+  if (check_diff_scene(scene, stages)) return -1;
+  if (B == 0 || n_nfe == 0 || wfe == 0) return 0;
+  cxk::KArgs ka{};
+  const int nb = scene->host.nb;
+  if (cxk::pack_judge(judge, nb * 6, nb, ka.judge, g_err) || cxk::pack_control(control, nb, ka.ctl, g_err)) return -1;
+  ka.geom = geom;
+  ka.gstride = geom_stride;
+  ka.B = B;
+  ka.n_steps = n_nfe * wfe;
+  ka.nfe_len = wfe;
+  ka.dt = dt;
+  ka.stages = stages & ~COTIX_STAGE_BROADPHASE;  // (as cotix_rollout_backward_ex2)
+  ka.save_dyn = const_cast<float*>(saved_dyn);
+  ka.save_keys = const_cast<uint32_t*>(saved_keys);
+  ka.tape = const_cast<uint32_t*>(tape);
+  ka.tw = cxk::tape_words(nb, scene->host.nc, scene->host.poly);
+  ka.judge_rec = const_cast<uint32_t*>(judge_rec);
+  ka.grad_control = grad_control;
+  ka.grad_dyn = grad_dyn0;
+  ka.grad_action = grad_dv;
+  return launch(scene, ka, 6, stream);
+}
+
 int cotix_physics_euler(float* dyn, int n_bodies, int B, float dt, cotix_stream_t stream) {
   if (!dyn) return fail("null argument");
   long long n = (long long)n_bodies * B;

@@ -104,7 +104,9 @@ struct PhaseAcc {
 #endif
 // MODE 0: step, 1: rollout forward (saves + return, + tape), 2: rollout
 // backward re-playing the forward, 3: eval with the device judge / control
-// (cotix_eval), 4: rollout backward from the forward's tape;
+// (cotix_eval), 4: rollout backward from the forward's tape, 5: the eval
+// that also saves (cotix_eval_rollout: run_wave ESAVE), 6: its tape backward
+// (cotix_eval_backward: run_wave_backward_tape EV);
 // SPEC: scene specialization (cxk::SPEC_*, compile-time dimensions);
 // GP (MODE 2 and 4): the backward with the body parameters' gradient
 // (KArgs::grad_params) -- instantiations of their own, so a launch that does
@@ -143,8 +145,8 @@ __global__ __launch_bounds__(WPB * 64) void step_kernel(cxk::KArgs a) {
   // the forward programs load the wave's state before the barrier: it writes
   // only the wave's own tile (disjoint from the tables), so its global reads
   // overlap the table copy's (a launch's fixed cost, K = 1 RL loops)
-  if (MODE != 2 && MODE != 4 && env0 < a.B) {
-    if (MODE == 3)
+  if (MODE != 2 && MODE != 4 && MODE != 6 && env0 < a.B) {
+    if (MODE == 3 || MODE == 5)
       cxk::ph_load_fwd<EW, false, true>(a, c, t, env0, lane);
     else
       cxk::ph_load_fwd<EW, MODE == 1>(a, c, t, env0, lane);
@@ -158,7 +160,11 @@ __global__ __launch_bounds__(WPB * 64) void step_kernel(cxk::KArgs a) {
   if (env0 >= a.B) return;  // whole wave idle (after the only workgroup barrier)
   PhaseAcc pa;
   const WaveRun run = pa.run(lane);
-  if (MODE == 4)
+  if (MODE == 6)
+    cxk::run_wave_backward_tape<EW, FNSET, false, true>(a, c, t, env0, run);
+  else if (MODE == 5)
+    cxk::run_wave<EW, FNSET, false, true, false, true>(a, c, t, env0, run, true);
+  else if (MODE == 4)
     cxk::run_wave_backward_tape<EW, FNSET, GP>(a, c, t, env0, run);
   else if (MODE == 2)
     cxk::run_wave_backward<EW, FNSET, GP>(a, c, t, env0, run);

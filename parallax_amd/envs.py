@@ -256,6 +256,23 @@ class AffineControl(_Frozen, AbstractControl):
                 c.clip_lo[i], c.clip_hi[i] = self.clip[i]
         return c
 
+    def params(self):
+        """The 26 differentiable parameters as a float32 [26] tensor (CPU):
+        gain[0][0..5], gain[1][0..5], target[0][0..5], target[1][0..5], bias
+        (the layout of cotix_eval_backward's grad_control rows)."""
+        return torch.tensor([*self.gain[0], *self.gain[1], *self.target[0], *self.target[1], *self.bias],
+                            dtype=torch.float32)
+
+    def with_params(self, theta):
+        """A new AffineControl on the same body with the same clip, its gain,
+        target and bias taken from the detached values of theta [26] (params()'s
+        layout); this control stays as it is."""
+        th = [float(v) for v in torch.as_tensor(theta).detach().to("cpu", torch.float32).reshape(-1)]
+        if len(th) != 26:
+            raise ValueError("AffineControl.with_params: theta has 26 entries (gain 2x6, target 2x6, bias 2)")
+        return AffineControl(self.body, [th[0:6], th[6:12]], [th[12:18], th[18:24]], (th[24], th[25]),
+                             None if self.clip is None else [tuple(p) for p in self.clip])
+
     def dv(self, state):
         out = []
         for i in range(2):
