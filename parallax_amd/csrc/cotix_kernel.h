@@ -43,11 +43,24 @@ struct Stats {
   unsigned long long valid_cands, fit64;  // valid candidates of the active items; wave-steps where they fit 64 lanes
   unsigned long long bp_cand, bp_guard_fail;  // broadphase: pairs past the gap test; of them, not certified by bp_guard
   unsigned long long epa_runs;                // polygon contacts whose GJK hit (EPA ran, not a self pair)
+  // the fused scan's active items by the list position at which they settle
+  // (the winning candidate's index in its cell's list): 0..15, [16] >= 16,
+  // [17] the list ran out with no passing candidate
+  unsigned long long settle[18];
 };
 inline Stats g_stats{};
+// every lane's two owner items at the end of a fused scan, for the tool's own
+// replays: the settle position (-1: the item was not active; the list's
+// length: it ran out) and the list's length (tools/collider_stats_emu.cpp)
+inline void (*g_settle_hook)(int lane, int at0, int len0, int at1, int len1) = nullptr;
 #define CXK_STAT(f, v) (cxk::g_stats.f += (unsigned long long)(v))
 #else
 #define CXK_STAT(f, v) ((void)0)
+#endif
+// the test builds of the host emulation count the items that the fused
+// scan's round 0 settled or finished (m_spec): a test's proof that it ran
+#ifdef COTIX_EMU_POISON
+inline unsigned long long g_emu_round0_done = 0;
 #endif
 // sub-phase cycle timers of the phase-timing build (tools/phase_prof.py):
 // CXK_SUB_T0 / CXK_SUB_T1(k) add the wave's clock delta to slot k (ad-hoc
@@ -2370,6 +2383,9 @@ CX_DEV uint32_t m_draw(const Ctx& c, Tile<EW> t, uint32_t sw, int q, int kso, bo
 // an owner's item (owner slot s of lane l: item id = l + 64 s)
 struct MItem {
   int cb = 0, ce = 0, cell = 0, pos = 0, e = 0;
+#ifdef COTIX_STATS
+  int at = -1;  // the list position the item settled at (the list's length: it ran out)
+#endif
 };
 template <int EW>
 CX_DEV MItem m_item(const Ctx& c, Tile<EW> t, int id) {
@@ -2391,6 +2407,29 @@ struct MConst {
   MItem it[2];
   uint32_t cm[2][2] = {{0u, 0u}, {0u, 0u}};
 };
+// and, for the speculative round 0 (m_spec, SM candidates per item), the
+// contact ids of each owner item's first SM candidates, a byte each (contact
+// ids are below MAXC = 256).  A type of its own, empty at SM = 0: the kernels
+// without a round 0 hold nothing for it.
+constexpr int SCAN_M_MAX = 8;
+template <int SM>
+struct MSpecIds {
+  static_assert(SM > 0 && SM <= SCAN_M_MAX && MAXC <= 256, "a byte per contact id, two words per item");
+  uint32_t w[2][(SM + 3) / 4] = {};
+};
+template <>
+struct MSpecIds<0> {};
+template <int EW, int SM>
+CX_DEV void ms_fetch(const Ctx& c, Tile<EW> t, int lane, const MConst& m, MSpecIds<SM>& ms) {
+  if constexpr (SM > 0) {
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      if (lane + s * WAVE >= c.nl * EW) continue;
+      for (int q = 0; q < SM && m.it[s].cb + q < m.it[s].ce; ++q)
+        ms.w[s][q >> 2] |= ((t.tb[c.sh.o_cand + m.it[s].cb + q] >> 18) & 255u) << (8 * (q & 3));
+    }
+  }
+}
 template <int EW>
 CX_DEV void mc_fetch(const Ctx& c, Tile<EW> t, int lane, MConst& m) {
   const SceneHdr& sc = c.sh;
@@ -2422,14 +2461,76 @@ CX_DEV bool m_settle(Tile<EW> t, MItem& it, bool drew, uint64_t bits, uint32_t w
   if (!drew) return true;  // (past the last rank: waits for a later round)
   if (bits != 0ull) {
     t.w(it.cell, it.e) = wcd;  // the winning candidate word
+#ifdef COTIX_STATS
+    const int at = it.pos + __builtin_ctzll(bits);
+    it.at = at;
+    CXK_STAT(settle[at < 16 ? at : 16], 1);
+#endif
     return false;
   }
   it.pos += G;
+#ifdef COTIX_STATS
+  if (it.cb + it.pos >= it.ce) {
+    it.at = it.ce - it.cb;
+    CXK_STAT(settle[17], 1);
+  }
+#endif
   return it.cb + it.pos < it.ce;
 }
-template <int EW, bool L1 = false>
+// Round 0 of the fused scan from the helper wave's speculative draw word
+// (scan_spec_fill: bit m is the bernoulli draw of the cell's candidate cb + m,
+// m < min(SM, list length), made ahead of the physics).  The owner ANDs it
+// with the validity of those candidates -- the env's contact-valid mask at
+// their contact ids, which it holds packed a byte each (ids, ms_fetch) -- and
+// the lowest set bit is the scan's first passing candidate: the cell is
+// written.  Otherwise the scan goes on lazily from position min(SM, length);
+// returns "still pending".
+template <int EW, int SM>
+CX_DEV bool m_spec(const Ctx& c, Tile<EW> t, MItem& it, int id, const uint32_t* ids, int ksp) {
+  const SceneHdr& sc = c.sh;
+  const uint32_t w = t.u[ksp * EW + id];  // [cell][env]: item id's word
+  uint32_t ok = 0u;
+  if (sc.nmw <= 2) {
+    const uint64_t vv = (uint64_t)t.w(c.L.vm, it.e) | (sc.nmw > 1 ? (uint64_t)t.w(c.L.vm + 1, it.e) << 32 : 0ull);
+#pragma unroll
+    for (int m = 0; m < SM; ++m) ok |= (uint32_t)((vv >> ((ids[m >> 2] >> (8 * (m & 3))) & 255u)) & 1ull) << m;
+  } else {
+#pragma unroll
+    for (int m = 0; m < SM; ++m) {
+      const int cid = (int)((ids[m >> 2] >> (8 * (m & 3))) & 255u);
+      ok |= ((t.w(c.L.vm + (cid >> 5), it.e) >> (cid & 31)) & 1u) << m;
+    }
+  }
+  const uint32_t bits = w & ok;  // (past the list's end: the helper's bit is 0)
+  const int len = it.ce - it.cb;
+  if (bits != 0u) {
+    t.w(it.cell, it.e) = t.tb[sc.o_cand + it.cb + __builtin_ctz(bits)];  // the winning candidate word
+#ifdef COTIX_STATS
+    it.at = __builtin_ctz(bits);
+    CXK_STAT(settle[it.at], 1);
+#endif
+#ifdef COTIX_EMU_POISON
+    ++g_emu_round0_done;
+#endif
+    return false;
+  }
+  it.pos = len < SM ? len : SM;
+#ifdef COTIX_STATS
+  if (it.pos >= len) {
+    it.at = len;
+    CXK_STAT(settle[17], 1);
+  }
+#endif
+#ifdef COTIX_EMU_POISON
+  if (it.pos >= len) ++g_emu_round0_done;
+#endif
+  return it.pos < len;
+}
+// SM > 0: round 0 is m_spec's, from this step's speculative draw words (ksp:
+// their first word in the tile's addressing; < 0: the step has none)
+template <int EW, bool L1 = false, int SM = 0>
 CX_DEV void ph_M_fused(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, int lane, int kso, const MConst& mc,
-                       int kl1 = 0, int ko1 = 0) {
+                       int kl1 = 0, int ko1 = 0, int ksp = -1, const MSpecIds<SM>& ms = MSpecIds<SM>{}) {
   const bool two = c.nl * EW > WAVE;  // uniform (a constant in the specialized kernels)
   MItem it0 = mc.it[0], it1 = mc.it[1];
   const bool f0 = m0_active_c<EW>(a, c, t, env0, lane, mc.cm[0]);
@@ -2458,6 +2559,16 @@ CX_DEV void ph_M_fused(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, int l
     }
   }
 #endif
+  if constexpr (SM > 0) {
+    if (ksp >= 0) {  // (uniform: a launch's first half has no draw words)
+      const bool k0 = f0 && m_spec<EW, SM>(c, t, it0, lane, ms.w[0], ksp);
+      pend0 = ballot(k0);
+      if (two) {
+        const bool k1 = f1 && m_spec<EW, SM>(c, t, it1, lane + WAVE, ms.w[1], ksp);
+        pend1 = ballot(k1);
+      }
+    }
+  }
   for (int round = 0; (pend0 | pend1) != 0ull; ++round) {
 #ifdef COTIX_STATS
     if (lane == 0) {
@@ -2493,6 +2604,10 @@ CX_DEV void ph_M_fused(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, int l
       pend1 = ballot(k1);
     }
   }
+#ifdef COTIX_STATS
+  if (g_settle_hook != nullptr)
+    g_settle_hook(lane, f0 ? it0.at : -1, it0.ce - it0.cb, f1 ? it1.at : -1, it1.ce - it1.cb);
+#endif
 }
 
 // phase D: choose_random_contact (cotix/_colliders.py:274-295)
@@ -4195,9 +4310,11 @@ CX_DEV void transform_phases(const KArgs& a, const Ctx& c, Tile<EW> t, int env0,
 // TAPE: the rollout forward with a tape (phase B records EPA's edges)
 // L1: the fused scan reads its first-level keys from the level-1 key ring
 // (kl1: this step's slot, m_draw)
-template <int EW, int FNSET, bool PRE, class R, bool AB = false, bool TAPE = false, bool L1 = false>
+// SM, ksp: the fused scan's speculative round 0 and this step's draw words
+template <int EW, int FNSET, bool PRE, class R, bool AB = false, bool TAPE = false, bool L1 = false, int SM = 0>
 CX_DEV void collider_phases(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, const R& run, int slot, int kso,
-                            const MConst& mc, int step = 0, int kl1 = 0, int ko1 = 0) {
+                            const MConst& mc, int step = 0, int kl1 = 0, int ko1 = 0, int ksp = -1,
+                            const MSpecIds<SM>& ms = MSpecIds<SM>{}) {
   if (!AB && !CXK_SKIP(a, 1)) transform_phases<EW, FNSET>(a, c, t, env0, run);
   if ((FNSET & FNS_CONVEX) != 0 && c.sh.poly && (a.stages & COTIX_STAGE_BROADPHASE) && !CXK_SKIP(a, 2)) {
     run(PH_BP0, [&](int l) { ph_BP0<EW>(a, c, t, env0, l); });
@@ -4227,7 +4344,7 @@ CX_DEV void collider_phases(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, 
     }
   }
   if (!CXK_SKIP(a, 4) && c.nl > 0 && scan_fused<EW>(c)) {
-    run(PH_C1, [&](int l) { ph_M_fused<EW, L1>(a, c, t, env0, l, kso, mc, kl1, ko1); });
+    run(PH_C1, [&](int l) { ph_M_fused<EW, L1, SM>(a, c, t, env0, l, kso, mc, kl1, ko1, ksp, ms); });
   } else if (!CXK_SKIP(a, 4) && c.nl > 0) {
     for (int ch = 0; ch * WAVE < c.nl * EW; ++ch) {
       run(PH_C0, [&](int l) { ph_C0<EW>(a, c, t, env0, l, ch); });
@@ -4394,14 +4511,59 @@ CX_HD int key_l1_keys(const SceneHdr& s, const uint32_t* tb) {
 // of the helper form with it (nk1: key_l1_keys)
 template <int EW>
 CX_HD int key_l1_ring_words(int nk1) { return 2 * KL1R * 2 * nk1 * EW; }
+// (spec: with the speculative draw ring that follows the key rings --
+// scan_spec_fill -- one word per (cell, env) item and step, two halves)
 template <int EW>
-CX_HD size_t help_l1_lds_bytes(const SceneHdr& s, int wpb, int nk1) {
-  return help_lds_bytes<EW>(s, wpb) + 4 * (size_t)wpb * key_l1_ring_words<EW>(nk1);
+CX_HD int scan_spec_ring_words(const SceneHdr& s) { return 2 * KL1R * (int)s.nl * EW; }
+template <int EW>
+CX_HD size_t help_l1_lds_bytes(const SceneHdr& s, int wpb, int nk1, bool spec = false) {
+  return help_lds_bytes<EW>(s, wpb) +
+         4 * (size_t)wpb * (key_l1_ring_words<EW>(nk1) + (spec ? scan_spec_ring_words<EW>(s) : 0));
 }
 // the barriers of a launch in this form: one per ring half, a window's with
 // its first half's (step waves, helper waves and idle waves all pass this many)
 CX_HD int key_l1_barriers(const KArgs& a) {
   return keys_on(a) && a.n_steps > 0 ? (a.n_steps + KL1R - 1) / KL1R : 0;
+}
+// ---------------------------------------------------------------------------
+// The speculative draw words (the key helper's third job).  A scan candidate's
+// bernoulli draw bernoulli(split(split(ring key, N1)[i1])[0]) depends on the
+// step's keys and the candidate's scene-constant indices only; the physics
+// decides just which cells are active and which candidates are NaN.  Each
+// cell's list is in reverse scan order, so the scan reaches its first SCAN_M
+// candidates first: after a half's level-1 keys the helper draws those, for
+// every step of the half and every (cell, env) item, into one word per item
+// (bit m: candidate cb + m's draw, m_draw's L1 expression without `& valid`),
+// and the step wave's round 0 (m_spec) settles from it every item whose first
+// valid passing candidate lies among them.  The words live in a second ring of
+// the same two halves, [step in ring][cell][env], filled in the same helper
+// call as the keys they derive from and released by the same barrier -- from
+// a launch's second half on (key_l1_next): steps 0 .. KL1R - 1 scan lazily.
+// A help policy takes part by declaring `static constexpr int spec = SCAN_M`
+// and `int spo`, the ring's first word from the tile's in tile words.
+// ---------------------------------------------------------------------------
+// candidates drawn ahead per item (a power of two, <= SCAN_M_MAX); another
+// value is an A/B build's knob (profiles/scan_spec_ab_*.json)
+#ifndef COTIX_SCAN_M
+#define COTIX_SCAN_M 4
+#endif
+constexpr int SCAN_M = COTIX_SCAN_M;
+static_assert(SCAN_M > 0 && SCAN_M <= SCAN_M_MAX && (SCAN_M & (SCAN_M - 1)) == 0 && WAVE % SCAN_M == 0,
+              "an item's draws are SCAN_M consecutive lanes of one pass");
+template <class H, class = void>
+struct help_spec {
+  static constexpr int value = 0;
+};
+template <class H>
+struct help_spec<H, decltype((void)H::spec)> {
+  static constexpr int value = H::spec;
+};
+template <class H>
+CX_MF int help_spo(const H& h) {
+  if constexpr (help_spec<H>::value > 0)
+    return h.spo;
+  else
+    return 0;
 }
 template <int EW>
 struct KeyL1 {
@@ -4410,7 +4572,44 @@ struct KeyL1 {
   int nk1 = 0;     // keys per env-step
   int s0 = 0;      // the next half's first step
   int q = 0;       // barriers reached
+  int sm = 0;      // candidates drawn ahead per item (0: no draw ring)
+  int spo = 0;     // the draw ring's first word from kh.tm's, in tile words
 };
+// the draw words of steps s0 .. s0 + n - 1 from their slots of the key ring
+// (key_l1_fill's, complete).  Lanes are (step, cell, env, m) items, m fastest,
+// 64 / M items a pass; an item's bits come from the pass's ballot and its
+// m = 0 lane stores them.
+template <int EW>
+CX_DEV void scan_spec_fill(const Ctx& c, Tile<EW> tr, int l1o, int nk1, int spo, int M, int s0, int n, int lane) {
+  using namespace cx;
+  const SceneHdr& sc = c.sh;
+  const bool part = sc.prng != 0;
+  const int NI = c.nl * EW;  // items per step
+#ifdef COTIX_EMU_POISON
+  // test instrumentation: the half's previous words die here
+  for (int w = lane; w < KL1R * NI; w += WAVE) tr.u[(spo + (s0 % (2 * KL1R)) * c.nl) * EW + w] = 0x7FBADBADu;
+  lockstep();
+#endif
+  const int total = n * NI * M;
+  for (int base = 0; base < total; base += WAVE) {
+    const int x = base + lane, m = x % M, id = (x / M) % NI, s = s0 + x / (M * NI);
+    const int l = id / EW, e = id % EW;
+    bool pass = false;
+    if (x < total && m < tr.ti(sc.o_ccnt + l)) {
+      const uint32_t cd = tr.tb[sc.o_cand + tr.ti(sc.o_cbeg + l) + m];
+      const int i1 = cd & 511u, i2 = (cd >> 9) & 511u, ty = cd >> 27;
+      int ko = i2;  // the key's index in the ring slot (m_draw's)
+      for (int p = 0; p + 1 < c.nt; ++p) ko += p < ty ? tr.ti(sc.o_tn2 + p) : 0;
+      const int kl1 = l1o + (s % (2 * KL1R)) * 2 * nk1;
+      const key2 k2 = key2{tr.w(kl1 + 2 * ko, e), tr.w(kl1 + 2 * ko + 1, e)};
+      const key2 k = split_at_l(k2, (uint32_t)tr.ti(sc.o_tn1 + ty), (uint32_t)i1, part);
+      pass = bernoulli_l(split_at_l(k, 2u, 0u, part), sc.pc, part);
+    }
+    const uint64_t pm = ballot(pass);
+    if (x < total && m == 0)
+      tr.u[(spo + (s % (2 * KL1R)) * c.nl) * EW + id] = (uint32_t)(pm >> lane) & ((1u << M) - 1u);
+  }
+}
 // the ring half of steps s0 .. s0 + n - 1 from the type keys of their window
 // (tk: the buffer that holds it).  Items (key block, env), a step at a time.
 // Legacy layout: block j of split(skey_t, N) gives flat words j and N + j
@@ -4474,6 +4673,13 @@ CX_DEV void key_l1_next(const KArgs& a, const Ctx& c, KeyL1<EW>& h, const R& run
   const int w = h.s0 / KWIN, n = a.n_steps - h.s0 < KL1R ? a.n_steps - h.s0 : KL1R;
   const Tile<EW> tk = (w == 0 || (w & 1)) ? kh.th : kh.tm;
   run(PH_K, [&](int l) { key_l1_fill<EW>(c, kh.tm, tk, h.l1o, h.nk1, h.s0, n, l); });
+  // the half's draw words, from the keys just written (a phase of their own:
+  // other lanes' keys).  Not for a launch's first half: the step wave waits
+  // for that one at its first scan with nothing to run meanwhile, so draws
+  // made there are not ahead of anything -- they would delay every launch by
+  // their whole cost (measured: 1.7 % slower than without draw words)
+  if (h.sm > 0 && h.s0 > 0)
+    run(PH_K, [&](int l) { scan_spec_fill<EW>(c, kh.tm, h.l1o, h.nk1, h.spo, h.sm, h.s0, n, l); });
   h.s0 += KL1R;
 }
 
@@ -4497,6 +4703,9 @@ CX_DEV void run_wave(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, const R
   constexpr bool L1 = help_l1<H>::value;
   static_assert(!L1 || H::on, "the level-1 key ring is the key helper's");
   const int nk1 = L1 ? key_l1_keys(c.sh, t.tb) : 0, ko1 = L1 && c.nt > 0 ? t.ti(c.sh.o_tn2) : 0;
+  // the speculative draw words (a help policy's `spec`): the scan's round 0
+  constexpr int SM = help_spec<H>::value;
+  static_assert(SM == 0 || L1, "the speculative draws read the level-1 key ring");
   if (EVAL && a.judge.on) {  // the first NFE's start
     run(PH_J, [&](int l) {
       ph_JB<EW>(a, c, t, env0, l);
@@ -4513,8 +4722,12 @@ CX_DEV void run_wave(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, const R
   BConst bc;
   if (bconst) run(PH_B, [&](int l) { bc_fetch<EW>(c, t, l, bc); });
   MConst mc;  // the fused scan's launch-constant owner words
+  MSpecIds<SM> ms;  // (and its round 0's)
   if ((a.stages & COTIX_STAGE_COLLIDER) && c.nl > 0 && scan_fused<EW>(c))
-    run(PH_C1, [&](int l) { mc_fetch<EW>(c, t, l, mc); });
+    run(PH_C1, [&](int l) {
+      mc_fetch<EW>(c, t, l, mc);
+      ms_fetch<EW, SM>(c, t, l, mc, ms);
+    });
   RetRegs rr;  // the rollout's return terms
   if (ROLL) run(PH_RET, [&](int l) { ret_fetch<EW>(c, t, l, rr); });
   // the actions one step ahead (act_fetch): an the next step's, ac this step's
@@ -4574,6 +4787,8 @@ CX_DEV void run_wave(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, const R
     // (key_l1_next), passed before the step's scan
     const int kl1 = L1 ? help_l1o(help) + (step % (2 * KL1R)) * 2 * nk1 : 0;
     const bool l1bar = L1 && keys && step % KL1R == 0 && !(slot == 0 && step > 0);  // (else the window's)
+    // its draw words, of the same half (none in a launch's first: scan_spec_fill's note)
+    const int ksp = SM > 0 && step >= KL1R ? help_spo(help) + (step % (2 * KL1R)) * c.nl : -1;
     // phases A, T, B as one (circle / AABB scenes whose contact items fit the
     // phase's ABQ prefetched chunks; uniform)
     if (bconst) {  // phase A, then B from the launch-constant item words (no phase T)
@@ -4584,7 +4799,8 @@ CX_DEV void run_wave(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, const R
       if (a.stages & COTIX_STAGE_COLLIDER) run(PH_B, [&](int l) { ph_B_const<EW>(a, c, t, env0, l, bc); });
       if (l1bar) help.bar();
       if (a.stages & COTIX_STAGE_COLLIDER)
-        collider_phases<EW, FNSET, true, R, true, SAVE, L1>(a, c, t, env0, run, slot, kso, mc, step, kl1, ko1);
+        collider_phases<EW, FNSET, true, R, true, SAVE, L1, SM>(a, c, t, env0, run, slot, kso, mc, step, kl1, ko1,
+                                                                ksp, ms);
     } else if (FNSET == FNS_ANALYTIC && c.nc * EW <= ABQ * WAVE) {
       // stage 1 reads the pre-Euler state: every read is issued before phase
       // A's writes (stage 2); stage 3 computes the contacts
@@ -4596,8 +4812,8 @@ CX_DEV void run_wave(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, const R
           },
           [&](int l, const ABRegs& r) { ab_contacts<EW>(a, c, t, env0, l, r); });
       if (l1bar) help.bar();
-      if (a.stages & COTIX_STAGE_COLLIDER) collider_phases<EW, FNSET, true, R, FNSET == FNS_ANALYTIC, SAVE, L1>(
-          a, c, t, env0, run, slot, kso, mc, step, kl1, ko1);
+      if (a.stages & COTIX_STAGE_COLLIDER) collider_phases<EW, FNSET, true, R, FNSET == FNS_ANALYTIC, SAVE, L1, SM>(
+          a, c, t, env0, run, slot, kso, mc, step, kl1, ko1, ksp, ms);
     } else {
       run(PH_A, [&](int l) {
         act_next(l, step);
@@ -4605,7 +4821,8 @@ CX_DEV void run_wave(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, const R
       });
       if (l1bar) help.bar();
       if (a.stages & COTIX_STAGE_COLLIDER)
-        collider_phases<EW, FNSET, true, R, false, SAVE, L1>(a, c, t, env0, run, slot, kso, mc, step, kl1, ko1);
+        collider_phases<EW, FNSET, true, R, false, SAVE, L1, SM>(a, c, t, env0, run, slot, kso, mc, step, kl1, ko1,
+                                                                 ksp, ms);
     }
     if (a.trace_chosen != nullptr || a.trace_cells != nullptr)
       run(PH_TRACE, [&](int l) { ph_trace<EW>(a, c, t, env0, l, step); });

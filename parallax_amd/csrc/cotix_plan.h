@@ -240,7 +240,8 @@ inline LaunchPlan plan_launch(const cxk::SceneDev& sc, int fnset, Variant v, con
     // of 512 threads) and LDS_CAP / lds by its LDS, and the launch needs no
     // more than its workgroups over the CUs
     const size_t lds0 = cxk::help_lds_bytes<4>(sc, WPB);
-    const size_t lds1 = cxk::help_l1_lds_bytes<4>(sc, WPB, cxk::key_l1_keys(sc, sc.hot));
+    // (and the speculative draw ring: the L1 kernels carry both)
+    const size_t lds1 = cxk::help_l1_lds_bytes<4>(sc, WPB, cxk::key_l1_keys(sc, sc.hot), true);
     const cxk::Ctx c4 = cxk::make_ctx<4>(sc);
     const int need = dev.cus > 0 ? ((int)p.grid + dev.cus - 1) / dev.cus : 2;
     const int res0 = std::min<int>(2, (int)(LDS_CAP / lds0)), res1 = std::min<int>(2, (int)(LDS_CAP / lds1));

@@ -243,11 +243,15 @@ struct GpuKeyHelp {
 };
 // L1: the helper also fills the level-1 key ring (cxk::KeyL1): WPB rings
 // follow the window buffers, and the workgroup passes cxk::key_l1_barriers
+// spec: and the speculative draw words (cxk::scan_spec_fill): WPB draw rings
+// follow the key rings
 struct GpuKeyHelpL1 {
   static constexpr bool on = true;
   static constexpr bool l1 = true;
+  static constexpr int spec = cxk::SCAN_M;
   int kwalt;
   int l1o;
+  int spo;
   __device__ __forceinline__ void bar() const { lds_barrier(); }
 };
 template <int FNSET, int SPEC, bool SDEFER, bool L1 = false>
@@ -292,12 +296,14 @@ __global__ __launch_bounds__(2 * WPB * 64) void step_help_kernel(cxk::KArgs a) {
   if constexpr (L1) {
     const int nk1 = cxk::key_l1_keys(sh, lds);
     const int l1o = (int)(lds + nhot + WPB * (rw + hw) + grp * cxk::key_l1_ring_words<EW>(nk1) - um) / EW;
+    const int spo = (int)(lds + nhot + WPB * (rw + hw + cxk::key_l1_ring_words<EW>(nk1)) +
+                          grp * cxk::scan_spec_ring_words<EW>(sh) - um) / EW;
     if (stepper) {
       // the step wave's instructions issue ahead of its helper's on their
       // SIMD: the launch is the step waves' dependent chain (measured: 701.7
       // -> 706.8 M env-steps/s, profiles/key_l1_ab_*.json)
       __builtin_amdgcn_s_setprio(2);
-      const GpuKeyHelpL1 help{(int)(hb - um) / EW - c.L.kw, l1o};
+      const GpuKeyHelpL1 help{(int)(hb - um) / EW - c.L.kw, l1o, spo};
       cxk::run_wave<EW, FNSET, false, false, SDEFER>(a, c, tm, env0, run, true, help);
     } else {
       cxk::KeyL1<EW> h;
@@ -306,6 +312,8 @@ __global__ __launch_bounds__(2 * WPB * 64) void step_help_kernel(cxk::KArgs a) {
       h.kh.env0 = env0;
       h.l1o = l1o;
       h.nk1 = nk1;
+      h.sm = cxk::SCAN_M;
+      h.spo = spo;
       for (int q = 0; q < nbar; ++q) {
         cxk::key_l1_next<EW>(a, c, h, run);
         lds_barrier();

@@ -3,6 +3,17 @@ phase-C items, candidate-scan rounds, resolutions and phase-F items, from the
 host emulation of the kernel built with -DCOTIX_STATS.
 
   python tools/collider_stats.py [--scenario robocup|lunar] [--envs 256] [--steps 64] [--ew 4] [--broadphase]
+
+--bench: the bench's own RoboCup workload -- the first --envs envs of its
+4096-env batch (perturbed balls, keys split(PRNGKey(3), 4096)), autoreset to the
+restart state, --settle steps run first on the C port (192: the steps after
+three 64-step launches).
+
+The fused scan's settle histogram: the list position at which each active item
+settles (its winning candidate's index in its cell's list; 0..15, >= 16, the
+list ran out), and from the same positions what a round 0 over each item's
+first M candidates would leave, M = 2, 4, 8: the items still pending and the
+lazy rounds they take, per wave-step (the scan's own round rule replayed).
 """
 import argparse
 import ctypes
@@ -26,9 +37,10 @@ def main():
     ap.add_argument("--ew", type=int, default=4)
     ap.add_argument("--broadphase", action="store_true", help="COTIX_STAGE_BROADPHASE (polygon scenes)")
     ap.add_argument("--drop", type=float, default=0.0, help="lunar: lower the lander and legs by this much (contact)")
+    ap.add_argument("--bench", action="store_true", help="robocup: the bench's own batch and restart state")
     ap.add_argument("--settle", type=int, default=0, help="driver steps run first on the C port (lunar settles by ~2560)")
     a = ap.parse_args()
-    src = os.path.join(ROOT, "tests", "emu", "cotix_emu.cpp")
+    src = os.path.join(ROOT, "tools", "collider_stats_emu.cpp")
     subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math",
                     "-DCOTIX_STATS", "-w", src, "-o", LIB], check=True)
     import emu
@@ -47,6 +59,9 @@ def main():
         d0 = tr["dyn"][0]  # [8 envs][5][6]
         dyn = np.ascontiguousarray(np.concatenate([d0] * (B // d0.shape[0] + 1))[:B].transpose(1, 2, 0))
         stages, gstride = 1 | 4 | 16, 0
+        if a.bench:
+            from cotix_oracle import cport
+            dyn, bench_keys = cport.robocup_batch(B, total=4096)
     else:
         tk = prng.split(prng.PRNGKey(0), B)
         rows, dyns = [], []
@@ -63,6 +78,8 @@ def main():
         dyn = np.ascontiguousarray(np.array(dyns, np.float32).transpose(1, 2, 0))
         stages = 1 | 2 | 4 | 8 | 16 | (32 if a.broadphase else 0)
     keys = np.ascontiguousarray(np.array(prng.split(prng.PRNGKey(3), B), np.uint32))
+    if a.scenario == "robocup" and a.bench:
+        keys = np.ascontiguousarray(bench_keys, np.uint32)
     dyn_reset = dyn.copy()
     err = np.zeros(B, np.uint32)
     if a.settle:  # the settled regime: advance on the C port (same bits), count the next steps only
@@ -71,11 +88,21 @@ def main():
         sc = cport.Scene(cport.load(), src_bodies)
         sc.step(dyn, keys, err, a.settle, stages, geom=None if gstride == 0 else geom, dyn_reset=dyn_reset, nthreads=8)
     out = (ctypes.c_ulonglong * 17)()
+    st = (ctypes.c_ulonglong * 24)()
     lib.emu_stats(out)
+    lib.emu_stats_settle(st)  # (arms the settle replay, clears its counters)
     emu.step(lib, h, dyn, keys, err, geom, gstride, a.steps, stages, E=a.ew, dyn_reset=dyn_reset)
+    lib.emu_stats_settle(st)
     lib.emu_stats(out)
     ws = max(out[0], 1)
-    print({"scenario": a.scenario, "envs": B, "steps": a.steps, "ew": a.ew,
+    hist = list(st[:18])
+    print({"scenario": a.scenario, "envs": B, "steps": a.steps, "ew": a.ew, "bench_workload": bool(a.bench),
+           "settled_first_on_c_port_steps": a.settle,
+           "settle_position_histogram": {**{str(q): hist[q] for q in range(16)}, ">=16": hist[16],
+                                         "list_exhausted": hist[17]},
+           "settle_position_share": [round(x / max(sum(hist), 1), 4) for x in hist],
+           "after_round0_of_M": {str(2 << k): {"items_left_per_wave_step": st[18 + k] / ws,
+                                               "lazy_rounds_per_wave_step": st[21 + k] / ws} for k in range(3)},
            "active_items_per_wave_step": out[1] / ws, "rounds_per_wave_step": out[2] / ws,
            "resolutions_per_env_step": out[3] / (B * a.steps), "f_items_per_wave_step": out[4] / ws,
            "b_items_per_wave_step": out[5] / ws, "valid_draw_frac": out[7] / max(out[6], 1),
