@@ -168,6 +168,13 @@ int cotix_scene_destroy(cotix_scene* scene);
 /* floats of local part geometry the scene expects per env (circle: r,cx,cy,0;
  * AABB: lo.x,lo.y,up.x,up.y; polygon: x,y per vertex), parts in order. */
 int cotix_scene_geom_floats(const cotix_scene* scene);
+/* ... of which the parts' words: cotix_scene_geom_floats minus the
+ * 4 * n_bodies parameter words a COTIX_SCENE_PER_ENV_BODY_PARAMS scene appends
+ * (GW, the rows of cotix_rollout_backward_ex3's grad_geom). */
+int cotix_scene_geom_part_words(const cotix_scene* scene);
+/* part `part`'s words in the geometry row: the offset of its first word and
+ * their count (4 for a circle or an AABB, 2 per polygon vertex). */
+int cotix_scene_part_geom(const cotix_scene* scene, int part, int* offset, int* count);
 /* introspection for tests: counts of distinct contacts / cells / candidates / type keys */
 int cotix_scene_info(const cotix_scene* scene, int* n_contacts, int* n_cells, int* n_candidates, int* n_types);
 /* Kernel variant of the scene's launches (no reference counterpart: a tiling
@@ -424,6 +431,37 @@ int cotix_rollout_backward_ex2(cotix_scene* scene, const float* saved_dyn, const
                                const uint32_t* tape, const float* geom, int geom_stride, int B, int n_steps, float dt,
                                int stages, const float* action, int action_body, const float* ret_weights,
                                float* grad_action, float* grad_dyn0, float* grad_params, cotix_stream_t stream);
+/* cotix_rollout_backward_ex2 plus the gradient of the return with respect to
+ * the shape geometry of every part (the remaining body leaves of the
+ * reference: Circle.radius / position, AABB.lower / upper,
+ * AbstractPolygon.vertices, cotix/_convex_shapes.py):
+ *   grad_geom device f32 [GW][B] (nullable), GW = cotix_scene_geom_part_words,
+ *        written (not accumulated): word [w][g] = d ret[g] / d word w of the
+ *        geometry row in its stored order -- circle (r, cx, cy, pad), AABB
+ *        (lo.x, lo.y, up.x, up.y), polygon x, y per vertex as uploaded --
+ *        summed over the rollout's steps; the env index last, as grad_params.
+ * Semantics are jax.grad's through the executed branches (collider choices,
+ * argmin / argmax and EPA's supports fixed, balanced ties).  Geometry enters
+ * the step only through the world parts: a circle's is (r, c + p), an AABB's
+ * (lo + p, up + p), a polygon's the rotated and translated local vertices in
+ * clockwise order (a constant permutation).  A circle's pad word gets an exact
+ * zero, an env in which nothing resolves exact zeros everywhere, NaN appears
+ * where the adjoint chain already carries it.
+ * Shared geometry (geom_stride == 0): [w][g] is env g's derivative with
+ * respect to the shared word; the gradient of a batch objective is the
+ * caller's sum over g.  Per-env rows (geom_stride > 0): with respect to env
+ * g's own word; a COTIX_SCENE_PER_ENV_BODY_PARAMS scene requires them (geom
+ * and geom_stride >= cotix_scene_geom_floats).
+ * With grad_geom == NULL this is cotix_rollout_backward_ex2 (the same kernels,
+ * the same bits); with it, grad_action, grad_dyn0 and grad_params keep their
+ * bits, the backward runs kernels of its own at one wave per env group, and a
+ * GJK / EPA contact's derivative is taken a second time inside the reverse
+ * chain for its parts' words.  The scene restrictions are ex2's. */
+int cotix_rollout_backward_ex3(cotix_scene* scene, const float* saved_dyn, const uint32_t* saved_keys,
+                               const uint32_t* tape, const float* geom, int geom_stride, int B, int n_steps, float dt,
+                               int stages, const float* action, int action_body, const float* ret_weights,
+                               float* grad_action, float* grad_dyn0, float* grad_params, float* grad_geom,
+                               cotix_stream_t stream);
 
 /* Differentiable eval: the gradient of cotix_eval's reward with respect to
  * the 26 parameters of the affine control and to the entry state, through the

@@ -52,6 +52,8 @@ SIGNATURES = {
     "cotix_scene_params": (_I, [_P, _P]),
     "cotix_scene_destroy": (_I, [_P]),
     "cotix_scene_geom_floats": (_I, [_P]),
+    "cotix_scene_geom_part_words": (_I, [_P]),
+    "cotix_scene_part_geom": (_I, [_P, _I, _P, _P]),
     "cotix_scene_info": (_I, [_P, _P, _P, _P, _P]),
     "cotix_scene_set_variant": (_I, [_P, _I, _I]),
     "cotix_scene_variant": (_I, [_P, _P, _P]),
@@ -66,6 +68,7 @@ SIGNATURES = {
     "cotix_rollout_ex": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _F, _I, _P, _I, _P, _P, _P, _P, _P, _P]),
     "cotix_rollout_backward_ex": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _F, _I, _P, _I, _P, _P, _P, _P]),
     "cotix_rollout_backward_ex2": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _F, _I, _P, _I, _P, _P, _P, _P, _P]),
+    "cotix_rollout_backward_ex3": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _F, _I, _P, _I, _P, _P, _P, _P, _P, _P]),
     "cotix_eval_rollout": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _I, ctypes.POINTER(CotixJudge),
                                 ctypes.POINTER(CotixControl), _P, _I, _P, _P, _P, _P, _P, _P, _P]),
     "cotix_eval_backward": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _I, ctypes.POINTER(CotixJudge),

@@ -12,8 +12,11 @@
 // so branch decisions are those the forward step took.
 //
 // Shape gradients use the geometry layout of the forward path: circle
-// (r, cx, cy, pad) and AABB (lo.x, lo.y, up.x, up.y); the radius is a
-// constant (not differentiated).
+// (r, cx, cy, pad) and AABB (lo.x, lo.y, up.x, up.y).  The body chain needs
+// the centres' and corners' cotangents only; the radius' cotangent (word 0 of
+// a circle) is computed on request -- GG, a compile-time flag of the circle
+// contacts' VJPs, for the shape geometry's gradient (KArgs::grad_geom); the
+// <false> instantiations are the code without it.
 //
 // Body parameters (mass, inertia, elasticity, friction_coefficient -- every
 // body leaf is differentiable in the reference, cotix/_bodies.py:140-154) are
@@ -87,6 +90,9 @@ CX_DEV void aabb_vs_aabb_vjp(const Shape& a, const Shape& b, v2 gpen, v2 gcp, fl
 }
 
 // circle_vs_circle (cotix/_contacts.py:30-58), contact branch
+// GG: ga[0] / gb[0] += the radii's cotangents (mn = min(dist - (ar + br), 0),
+// cp0 through br - ar)
+template <bool GG = false>
 CX_DEV void circle_vs_circle_vjp(const Shape& a, const Shape& b, v2 gpen, v2 gcp, float* ga, float* gb) {
   const v2 ap = v2{a.d(1), a.d(2)}, bp = v2{b.d(1), b.d(2)};
   const float ar = a.d(0), br = b.d(0);
@@ -102,11 +108,20 @@ CX_DEV void circle_vs_circle_vjp(const Shape& a, const Shape& b, v2 gpen, v2 gcp
   v2 gdir = scl(gpr, mn);
   float gdist = 0.0f, dummy = 0.0f;
   vjp_min(dist - (ar + br), 0.0f, dot(gpr, dir), &gdist, &dummy);
+  if (GG) {
+    ga[0] += -gdist;
+    gb[0] += -gdist;
+  }
   if (sides) {
     const v2 h = divs(gcp, 2.0f);
     gbp = add(gbp, h);
     gap = add(gap, h);
     gdir = add(gdir, scl(h, br - ar));
+    if (GG) {
+      const float gd = dot(h, dir);
+      gb[0] += gd;
+      ga[0] += -gd;
+    }
   } else if (circle_contains(a, bp)) {
     gbp = add(gbp, gcp);
   } else {
@@ -127,6 +142,9 @@ CX_DEV void circle_vs_circle_vjp(const Shape& a, const Shape& b, v2 gpen, v2 gcp
 }
 
 // circle_vs_aabb (cotix/_contacts.py:99-154), contact branch
+// GG: ga[0] += the radius' cotangent (the perfect-corner branch's r * unit(d),
+// the shifts' + r)
+template <bool GG = false>
 CX_DEV void circle_vs_aabb_vjp(const Shape& a, const Shape& b, v2 gpen, v2 gcp, float* ga, float* gb) {
   const v2 ap = v2{a.d(1), a.d(2)};
   const float r = a.d(0);
@@ -145,12 +163,14 @@ CX_DEV void circle_vs_aabb_vjp(const Shape& a, const Shape& b, v2 gpen, v2 gcp, 
     gap = sub(gap, gpen);
     gccp = add(gccp, gpen);
     const v2 gd = vjp_unit(d, scl(gpen, -r));
+    if (GG) ga[0] += -dot(gpen, divs(d, nrm(d)));
     gccp = add(gccp, gd);
     gap = sub(gap, gd);
   } else {  // pen = -shift[k] * dir[k]
     const float sh[4] = {(ap.y + r) - lo.y, up.y - (ap.y - r), (ap.x + r) - lo.x, up.x - (ap.x - r)};
     const int k = argmin_first(sh, 4);  // (selects, not a constant array: see aabb_vs_aabb_vjp)
     const float g = -(gpen.x * pick4(k, 0.0f, 0.0f, 1.0f, -1.0f) + gpen.y * pick4(k, 1.0f, -1.0f, 0.0f, 0.0f));
+    if (GG) ga[0] += g;  // every shift is ... + r
     switch (k) {
       case 0: gap.y += g; glo.y -= g; break;
       case 1: gup.y += g; gap.y -= g; break;
@@ -174,12 +194,14 @@ CX_DEV void circle_vs_aabb_vjp(const Shape& a, const Shape& b, v2 gpen, v2 gcp, 
   gb[3] += gup.y;
 }
 
-// reverse of run_contact for the analytic contacts
+// reverse of run_contact for the analytic contacts: ga / gb are the cotangents
+// of the two world shape words (GG: the circles' radius word too)
+template <bool GG = false>
 CX_DEV void contact_vjp(int fn, const Shape& a, const Shape& b, v2 gpen, v2 gcp, float* ga, float* gb) {
   switch (fn) {
     case FN_AABB_AABB: aabb_vs_aabb_vjp(a, b, gpen, gcp, ga, gb); break;
-    case FN_CIRCLE_CIRCLE: circle_vs_circle_vjp(a, b, gpen, gcp, ga, gb); break;
-    case FN_CIRCLE_AABB: circle_vs_aabb_vjp(a, b, gpen, gcp, ga, gb); break;
+    case FN_CIRCLE_CIRCLE: circle_vs_circle_vjp<GG>(a, b, gpen, gcp, ga, gb); break;
+    case FN_CIRCLE_AABB: circle_vs_aabb_vjp<GG>(a, b, gpen, gcp, ga, gb); break;
     default: break;  // polygon contacts are not differentiated (rejected on the host)
   }
 }
@@ -727,12 +749,12 @@ CX_DEV void fnormal_diff_vjp(v2 g, v2* ga, v2* gb) {
 // contact (not reached for a resolved contact)
 // (not inlined: its private point record and EPA buffer stay out of the
 // calling kernel's register allocation; only this rare pair pays the call)
-#if defined(__HIP__)
-__device__ __attribute__((noinline))
-#else
-static
-#endif
-bool circle_poly_vjp(const Shape& C, const Shape& P, const NarrowParams& np, v2 gpen, v2 gcp, v2* gc, VGrad& gv) {
+// GG: *gr += the radius' cotangent.  Every recorded point is unit(u) * r + c -
+// v, so the radius receives dot(g_k, unit(u_k)) of every point the reverse
+// walk visits; the contact point does not depend on r (only its branch does)
+template <bool GG>
+CX_DEV bool circle_poly_vjp_impl(const Shape& C, const Shape& P, const NarrowParams& np, v2 gpen, v2 gcp, v2* gc,
+                                 VGrad& gv, float* gr) {
   CPRec R;
   int e0 = -1, e1 = -1;
   if (!cp_forward(C, P, np, R, &e0, &e1)) return false;
@@ -760,6 +782,7 @@ bool circle_poly_vjp(const Shape& C, const Shape& P, const NarrowParams& np, v2 
       u = kd == CP_EPAN ? divs(fn, nrm(fn)) : (R.sg[k] > 0 ? fn : neg(fn));
     }
     const v2 gu = vjp_unit(u, scl(gp, r));
+    if (GG) *gr += dot(gp, divs(u, nrm(u)));
     if (kd == CP_NEG) {
       g[a] = sub(g[a], gu);
     } else if (kd == CP_FN) {
@@ -820,5 +843,20 @@ bool circle_poly_vjp(const Shape& C, const Shape& P, const NarrowParams& np, v2 
   }
   return true;
 }
+#if defined(__HIP__)
+#define CX_NOINLINE __device__ __attribute__((noinline))
+#else
+#define CX_NOINLINE static
+#endif
+CX_NOINLINE bool circle_poly_vjp(const Shape& C, const Shape& P, const NarrowParams& np, v2 gpen, v2 gcp, v2* gc,
+                                 VGrad& gv) {
+  return circle_poly_vjp_impl<false>(C, P, np, gpen, gcp, gc, gv, nullptr);
+}
+// ... and the radius' cotangent (the shape geometry's gradient)
+CX_NOINLINE bool circle_poly_vjp_r(const Shape& C, const Shape& P, const NarrowParams& np, v2 gpen, v2 gcp, v2* gc,
+                                   VGrad& gv, float* gr) {
+  return circle_poly_vjp_impl<true>(C, P, np, gpen, gcp, gc, gv, gr);
+}
+#undef CX_NOINLINE
 
 }  // namespace cx

@@ -282,6 +282,11 @@ struct KArgs {
   // d reward / d dv_t [n_steps][B][2], grad_dyn d reward / d the entry state
   uint32_t* judge_rec;
   float* grad_control;
+  // backward: [GW][B] d ret / d the parts' geometry words (the scene's
+  // geometry row in its stored order, without a per-env scene's parameter
+  // words: geom_part_words), summed over the steps, or null
+  // (cotix_rollout_backward_ex3; the GP == 2 programs below)
+  float* grad_geom;
 };
 
 // The judge record of the differentiable eval: one word per env and state
@@ -3715,6 +3720,23 @@ CX_DEV cx::Shape world_shape(const Ctx& c, Tile<EW> t, int p, int e) {
 // vertices, re-sorted: world slot k holds the local vertex whose transform
 // has its bits (phase TV1's exact arithmetic).  An AABB translates only
 // (corners [up, (up.x, lo.y), lo, (lo.x, up.y)]).
+// the cotangent of the world slot that holds local vertex (x, y) of a polygon
+// whose body is at (px, py) with (sin, cos) = (s, cs): first match, else zero
+CX_DEV cx::v2 slot_grad(const cx::Shape& W, const cx::VGrad& gv, float x, float y, float px, float py, float s,
+                        float cs) {
+  using namespace cx;
+  const float t0 = (cs * x + (-s) * y) + px * 1.0f, t1 = (s * x + cs * y) + py * 1.0f;
+  v2 g = v2{0.0f, 0.0f};
+  bool found = false;
+#pragma unroll
+  for (int k = 0; k < MAXV; ++k) {  // the slot holding this vertex (first match)
+    const bool hit = k < W.n && !found && W.w[2 * k] == t0 && W.w[2 * k + 1] == t1;
+    g.x = hit ? gv.x[k] : g.x;
+    g.y = hit ? gv.y[k] : g.y;
+    found = found || hit;
+  }
+  return g;
+}
 template <int EW>
 CX_DEV void part_pose_vjp(const Ctx& c, Tile<EW> t, int p, int e, const cx::Shape& W, const cx::VGrad& gv,
                           float* out) {
@@ -3733,16 +3755,7 @@ CX_DEV void part_pose_vjp(const Ctx& c, Tile<EW> t, int p, int e, const cx::Shap
   float gpx = 0.0f, gpy = 0.0f, gang = 0.0f;
   for (int j = 0; j < W.n; ++j) {
     const float x = t.f(lg + 2 * j, e), y = t.f(lg + 2 * j + 1, e);
-    const float t0 = (cs * x + (-s) * y) + px * 1.0f, t1 = (s * x + cs * y) + py * 1.0f;
-    v2 g = v2{0.0f, 0.0f};
-    bool found = false;
-#pragma unroll
-    for (int k = 0; k < MAXV; ++k) {  // the slot holding this vertex (first match)
-      const bool hit = k < W.n && !found && W.w[2 * k] == t0 && W.w[2 * k + 1] == t1;
-      g.x = hit ? gv.x[k] : g.x;
-      g.y = hit ? gv.y[k] : g.y;
-      found = found || hit;
-    }
+    const v2 g = slot_grad(W, gv, x, y, px, py, s, cs);
     gpx += g.x;
     gpy += g.y;
     gang += drot_dot(g, v2{x, y}, s, cs);
@@ -3771,6 +3784,72 @@ CX_DEV void gpar_zero(const KArgs& a, const Ctx& c, int env0, int lane) {
     for (int w = 0; w < 4 * c.nb; ++w) a.grad_params[(size_t)w * (size_t)a.B + (size_t)g] = 0.0f;
   }
 }
+// GP is a level: 0 none, 1 the body parameters (KArgs::grad_params), 2 the
+// shape geometry (KArgs::grad_geom) -- with the parameters when grad_params is
+// also given, a wave-uniform test in the level-2 programs only (a constant at
+// levels 0 and 1: they are the code they were)
+template <int GP>
+CX_DEV bool gpar_on(const KArgs& a) {
+  return GP == 1 || (GP == 2 && a.grad_params != nullptr);
+}
+// the shape geometry's gradient (KArgs::grad_geom [GW][B]), GP == 2 programs
+// only, by gpar_add's rule: env g's words belong to the lane that runs its
+// reverse chain, which zeroes them in the first phase and adds by plain
+// read-modify-write in one order -- steps T-1 .. 0; resolutions nb-1 .. 0;
+// part a's words ascending, then part b's -- so every form gives the same
+// bits.  No atomics, no tile words.  A circle's pad word is never added to.
+CX_HD int geom_part_words(const SceneHdr& sh) { return sh.epar != 0 ? (int)sh.epar - 1 : (int)sh.G; }
+CX_DEV void ggeo_add(const KArgs& a, int g, int w, float v) {
+  float* p = a.grad_geom + (size_t)w * (size_t)a.B + (size_t)g;
+  *p = *p + v;
+}
+template <int EW>
+CX_DEV void ggeo_zero(const KArgs& a, const Ctx& c, int env0, int lane) {
+  const int gw = geom_part_words(c.sh);
+  for (int e = lane; e < EW; e += WAVE) {
+    const int g = env0 + e;
+    if (g >= a.B) continue;
+    for (int w = 0; w < gw; ++w) a.grad_geom[(size_t)w * (size_t)a.B + (size_t)g] = 0.0f;
+  }
+}
+// an analytic contact's part: contact_vjp<true>'s cotangent of the world shape
+// words is the local words' (a circle's world form is (r, c + p), an AABB's
+// (lo + p, up + p): translation only)
+template <int EW>
+CX_DEV void ggeo_analytic(const KArgs& a, const Ctx& c, Tile<EW> t, int g, int p, int kind, const float (&gw)[4]) {
+  const int o = t.ti(c.sh.o_pgoff + p);
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+    if (k < 3 || kind != cx::KIND_CIRCLE) ggeo_add(a, g, o + k, gw[k]);
+}
+// a GJK / EPA contact's part from its world vertices' cotangent: polygon local
+// vertex j receives R^T g of the world slot that holds it (slot_grad, as
+// part_pose_vjp matches it); an AABB's corners [up, (up.x, lo.y), lo, (lo.x,
+// up.y)] fold to (lo.x, lo.y, up.x, up.y)
+template <int EW>
+CX_DEV void ggeo_part(const KArgs& a, const Ctx& c, Tile<EW> t, int g, int p, int e, const cx::Shape& W,
+                      const cx::VGrad& gv) {
+  using namespace cx;
+  const int go = t.ti(c.sh.o_pgoff + p);
+  if (W.kind == KIND_AABB) {
+    ggeo_add(a, g, go, gv.x[2] + gv.x[3]);
+    ggeo_add(a, g, go + 1, gv.y[1] + gv.y[2]);
+    ggeo_add(a, g, go + 2, gv.x[0] + gv.x[1]);
+    ggeo_add(a, g, go + 3, gv.y[0] + gv.y[3]);
+    return;
+  }
+  const Lay& L = c.L;
+  const int b = t.ti(c.sh.o_pbody + p), o = L.dyn + 6 * b, lg = L.geo + go;
+  const float px = t.f(o, e), py = t.f(o + 1, e);
+  float s, cs;
+  sincos32(t.f(o + 4, e), &s, &cs);
+  for (int j = 0; j < W.n; ++j) {
+    const float x = t.f(lg + 2 * j, e), y = t.f(lg + 2 * j + 1, e);
+    const v2 gj = slot_grad(W, gv, x, y, px, py, s, cs);
+    ggeo_add(a, g, go + 2 * j, cs * gj.x + s * gj.y);
+    ggeo_add(a, g, go + 2 * j + 1, (-s) * gj.x + cs * gj.y);
+  }
+}
 // a resolution's parameter cotangents (resolve_vjp<true>'s gq) of bodies i, j
 CX_DEV void gpar_resolution(const KArgs& a, int g, int i, int j, const float (&gq)[8]) {
 #pragma unroll
@@ -3780,7 +3859,7 @@ CX_DEV void gpar_resolution(const KArgs& a, int g, int i, int j, const float (&g
 }
 // GP: the masses' and inertias' cotangents of the lander and both legs, summed
 // over the four impulse pairs (in the reverse order), into env g's grad_params
-template <int EW, bool GP = false>
+template <int EW, int GP = 0>
 CX_DEV void joints_vjp(const Ctx& c, Tile<EW> t, int e, const KArgs* a = nullptr, int g_env = 0) {
   using namespace cx;
   const Lay& L = c.L;
@@ -3845,7 +3924,7 @@ CX_DEV void joints_vjp(const Ctx& c, Tile<EW> t, int e, const KArgs* a = nullptr
     gc1[f] = v2{0.0f, 0.0f};
     gc2[f] = v2{0.0f, 0.0f};
     float gq[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    fixed_vjp<GP>(pre1[f], m[0], c1[f], pre2[f], m[leg[f]], c2[f], g[0], g[leg[f]], gc1[f], gc2[f], gq);
+    fixed_vjp<GP != 0>(pre1[f], m[0], c1[f], pre2[f], m[leg[f]], c2[f], g[0], g[leg[f]], gc1[f], gc2[f], gq);
     if (GP) {
       gmI[0][0] += gq[0];
       gmI[0][1] += gq[1];
@@ -3853,7 +3932,7 @@ CX_DEV void joints_vjp(const Ctx& c, Tile<EW> t, int e, const KArgs* a = nullptr
       gmI[leg[f]][1] += gq[3];
     }
   }
-  if (GP) {
+  if (GP != 0 && gpar_on<GP>(*a)) {
 #pragma unroll
     for (int b = 0; b < 3; ++b) {
       gpar_add(*a, g_env, b, 0, gmI[b][0]);
@@ -3946,10 +4025,11 @@ CX_DEV void ph_GE(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, int lane) 
 // TILE: the adjoints are read from and written to the tile's adj words inside
 // the chain's own loops (g_regs: the one-wave form's schedule, the adjoints
 // live only across one step); otherwise the caller's registers carry them
-// GP: the body parameters' gradient too (gpar_resolution)
+// GP: the body parameters' (gpar_resolution) and the shape geometry's
+// (ggeo_analytic) gradients too, by level (gpar_on)
 // EV: the differentiable eval's step (the control's VJP, ctl_vjp; the seed
 // of every step, staged per env)
-template <int EW, int NB, bool TILE = false, bool GP = false, bool EV = false>
+template <int EW, int NB, bool TILE = false, int GP = 0, bool EV = false>
 CX_DEV void g_chain(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, int e, int step, float (&g)[NB][6],
                     GradOut* go = nullptr, CtlGrad* cg = nullptr) {
   using namespace cx;
@@ -3991,10 +4071,10 @@ CX_DEV void g_chain(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, int e, i
       Dyn gi = Dyn{g[i][0], g[i][1], g[i][2], g[i][3], g[i][4], g[i][5]};
       v2 gpen = v2{0.0f, 0.0f}, gcp = v2{0.0f, 0.0f};
       float gq[8];
-      resolve_vjp<GP>(bi, body_par<EW>(c, t, i, e), bj, body_par<EW>(c, t, j, e),
-                      v2{t.f(co, e), t.f(co + 1, e)}, v2{t.f(co + 2, e), t.f(co + 3, e)}, gi, gj, gpen, gcp, baum_of(sc),
-                      gq);
-      if (GP) gpar_resolution(a, env0 + e, i, j, gq);
+      resolve_vjp<GP != 0>(bi, body_par<EW>(c, t, i, e), bj, body_par<EW>(c, t, j, e),
+                           v2{t.f(co, e), t.f(co + 1, e)}, v2{t.f(co + 2, e), t.f(co + 3, e)}, gi, gj, gpen, gcp,
+                           baum_of(sc), gq);
+      if (GP != 0 && gpar_on<GP>(a)) gpar_resolution(a, env0 + e, i, j, gq);
       const int pa = t.ti(sc.o_cpa + cid), pb = t.ti(sc.o_cpb + cid), fn = t.ti(sc.o_cfn + cid);
       const int ka = t.ti(sc.o_pkind + pa), kb = t.ti(sc.o_pkind + pb);
       const int wa = L.world + t.ti(sc.o_pwoff + pa), wb = L.world + t.ti(sc.o_pwoff + pb);
@@ -4008,7 +4088,11 @@ CX_DEV void g_chain(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, int e, i
         SB.w[k] = t.f(wb + k, e);
       }
       float ga[4] = {0.0f, 0.0f, 0.0f, 0.0f}, gb[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-      contact_vjp(fn, SA, SB, gpen, gcp, ga, gb);
+      contact_vjp<GP == 2>(fn, SA, SB, gpen, gcp, ga, gb);
+      if (GP == 2) {
+        ggeo_analytic<EW>(a, c, t, env0 + e, pa, ka, ga);
+        ggeo_analytic<EW>(a, c, t, env0 + e, pb, kb, gb);
+      }
       const float gw[6] = {gi.px, gi.py, gi.vx, gi.vy, gi.a, gi.w}, hw[6] = {gj.px, gj.py, gj.vx, gj.vy, gj.a, gj.w};
 #pragma unroll
       for (int k = 0; k < 6; ++k) g[i][k] = gw[k];
@@ -4076,14 +4160,14 @@ CX_DEV void g_chain(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, int e, i
       for (int k = 0; k < 6; ++k) t.f(L.adj + 6 * b + k, e) = g[b][k];
   }
 }
-template <int EW, int NB, bool GP = false, bool EV = false>
+template <int EW, int NB, int GP = 0, bool EV = false>
 CX_DEV void g_regs(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, int e, int step, GradOut* go = nullptr,
                    CtlGrad* cg = nullptr) {
   float g[NB][6];
   g_chain<EW, NB, true, GP, EV>(a, c, t, env0, e, step, g, go, cg);
 }
 
-template <int EW, int FNSET = FNS_ANALYTIC, bool GP = false, bool EV = false>
+template <int EW, int FNSET = FNS_ANALYTIC, int GP = 0, bool EV = false>
 CX_DEV void ph_G(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, int lane, int step, GradOut* go = nullptr,
                  CtlGrad* cg = nullptr) {
   using namespace cx;
@@ -4119,10 +4203,10 @@ CX_DEV void ph_G(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, int lane, i
         Dyn gj = Dyn{t.f(aj, e), t.f(aj + 1, e), t.f(aj + 2, e), t.f(aj + 3, e), t.f(aj + 4, e), t.f(aj + 5, e)};
         v2 gpen = v2{0.0f, 0.0f}, gcp = v2{0.0f, 0.0f};
         float gq[8];
-        resolve_vjp<GP>(bi, body_par<EW>(c, t, i, e), bj, body_par<EW>(c, t, j, e),
-                        v2{t.f(co, e), t.f(co + 1, e)}, v2{t.f(co + 2, e), t.f(co + 3, e)}, gi, gj, gpen, gcp,
-                        baum_of(sc), gq);
-        if (GP) gpar_resolution(a, g, i, j, gq);
+        resolve_vjp<GP != 0>(bi, body_par<EW>(c, t, i, e), bj, body_par<EW>(c, t, j, e),
+                             v2{t.f(co, e), t.f(co + 1, e)}, v2{t.f(co + 2, e), t.f(co + 3, e)}, gi, gj, gpen, gcp,
+                             baum_of(sc), gq);
+        if (GP != 0 && gpar_on<GP>(a)) gpar_resolution(a, g, i, j, gq);
         // the contact: fn(world(part pa), world(part pb)); world = local + body position
         const int pa = t.ti(sc.o_cpa + cid), pb = t.ti(sc.o_cpb + cid), fn = t.ti(sc.o_cfn + cid);
         const int ka = t.ti(sc.o_pkind + pa), kb = t.ti(sc.o_pkind + pb);
@@ -4140,7 +4224,15 @@ CX_DEV void ph_G(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, int lane, i
           v2 gc = v2{0.0f, 0.0f};
           VGrad vb;
           vb.zero();
-          circle_poly_vjp(WA, WB, narrow_of(sc), gpen, gcp, &gc, vb);
+          if constexpr (GP == 2) {  // the circle's (r, c) -- its world centre is c + p -- then the polygon's vertices
+            float gr = 0.0f;
+            circle_poly_vjp_r(WA, WB, narrow_of(sc), gpen, gcp, &gc, vb, &gr);
+            const float gcw[4] = {gr, gc.x, gc.y, 0.0f};
+            ggeo_analytic<EW>(a, c, t, g, pa, KIND_CIRCLE, gcw);
+            ggeo_part<EW>(a, c, t, g, pb, e, WB, vb);
+          } else {
+            circle_poly_vjp(WA, WB, narrow_of(sc), gpen, gcp, &gc, vb);
+          }
           float gp[3] = {0.0f, 0.0f, 0.0f};
           part_pose_vjp<EW>(c, t, pb, e, WB, vb, gp);
           const int qa = L.adj + 6 * t.ti(sc.o_pbody + pa), qb = L.adj + 6 * t.ti(sc.o_pbody + pb);
@@ -4168,12 +4260,28 @@ CX_DEV void ph_G(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, int lane, i
 #pragma unroll
               for (int q = 0; q < 6; ++q) gp[q] += gk[k] * t.f(m + q, e);
             }
+            if (GP == 2) {
+              // the geometry needs the contact's VJP with its actual cotangent
+              // (phase GE's 4 x 6 pose responses cannot carry the parts' words):
+              // done here as in the branch below; the poses stay phase GE's
+              const Shape WA = world_shape<EW>(c, t, pa, e), WB = world_shape<EW>(c, t, pb, e);
+              VGrad va, vb;
+              va.zero();
+              vb.zero();
+              convex_contact_vjp(WA, WB, narrow_of(sc), gpen, gcp, va, vb);
+              ggeo_part<EW>(a, c, t, g, pa, e, WA, va);
+              ggeo_part<EW>(a, c, t, g, pb, e, WB, vb);
+            }
           } else {
             const Shape WA = world_shape<EW>(c, t, pa, e), WB = world_shape<EW>(c, t, pb, e);
             VGrad va, vb;
             va.zero();
             vb.zero();
             convex_contact_vjp(WA, WB, narrow_of(sc), gpen, gcp, va, vb);
+            if (GP == 2) {
+              ggeo_part<EW>(a, c, t, g, pa, e, WA, va);
+              ggeo_part<EW>(a, c, t, g, pb, e, WB, vb);
+            }
             part_pose_vjp<EW>(c, t, pa, e, WA, va, gp);
             part_pose_vjp<EW>(c, t, pb, e, WB, vb, gp + 3);
           }
@@ -4196,7 +4304,11 @@ CX_DEV void ph_G(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, int lane, i
           SB.w[k] = t.f(wb + k, e);
         }
         float ga[4] = {0.0f, 0.0f, 0.0f, 0.0f}, gb[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-        contact_vjp(fn, SA, SB, gpen, gcp, ga, gb);
+        contact_vjp<GP == 2>(fn, SA, SB, gpen, gcp, ga, gb);
+        if (GP == 2) {
+          ggeo_analytic<EW>(a, c, t, g, pa, ka, ga);
+          ggeo_analytic<EW>(a, c, t, g, pb, kb, gb);
+        }
         t.f(ai, e) = gi.px;
         t.f(ai + 1, e) = gi.py;
         t.f(ai + 2, e) = gi.vx;
@@ -4866,7 +4978,8 @@ CX_DEV void run_wave(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, const R
 // (recording the pre-resolution velocities), GE and G as in the re-play.
 // No key split, narrowphase, RNG scan or choice runs: the tape holds their
 // outcome, and every value the VJPs read is bit-identical to the re-play's
-// GP: with the body parameters' gradient (KArgs::grad_params, zeroed here)
+// GP: with the body parameters' gradient (KArgs::grad_params) and, at level
+// 2, the shape geometry's (KArgs::grad_geom), zeroed here
 // EV: the differentiable eval's backward (cotix_eval_backward): the forward
 // is the saving eval (run_wave ESAVE).  Each step re-applies the device
 // control on the restored state (euler_item EVAL: control_dv's own bits),
@@ -4876,7 +4989,7 @@ CX_DEV void run_wave(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, const R
 // from the last state's seed.  d reward / d dv goes out through grad_action,
 // the control's 26 parameter sums stay in the env lane's registers (CtlGrad)
 // until the end
-template <int EW, int FNSET, bool GP = false, bool EV = false, class R>
+template <int EW, int FNSET, int GP = 0, bool EV = false, class R>
 CX_DEV void run_wave_backward_tape(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, const R& run) {
   static_assert(!(GP && EV), "the eval backward does not carry the body parameters' gradient");
   CtlGrad cg;
@@ -4885,7 +4998,8 @@ CX_DEV void run_wave_backward_tape(const KArgs& a, const Ctx& c, Tile<EW> t, int
     return (l < EW && g < a.B) ? a.judge_rec[(size_t)ti * a.B + g] : 0u;
   };
   run(PH_ADJ, [&](int l) {
-    if (GP) gpar_zero<EW>(a, c, env0, l);
+    if (GP != 0 && gpar_on<GP>(a)) gpar_zero<EW>(a, c, env0, l);
+    if (GP == 2) ggeo_zero<EW>(a, c, env0, l);
     ws_poly_init<EW>(c, t, l);
     ph_geo<EW>(a, c, t, env0, l);
     if (EV) {
@@ -5129,11 +5243,13 @@ CX_DEV void run_backward_split(const KArgs& a, const Ctx& c, Tile<EW> t0, Tile<E
 
 // backward: steps n_steps-1 .. 0, each re-played from the saved state (so
 // every discrete choice is the forward's) and then reversed by phase G
-// GP: with the body parameters' gradient (KArgs::grad_params, zeroed here)
-template <int EW, int FNSET, bool GP = false, class R>
+// GP: with the body parameters' gradient (KArgs::grad_params) and, at level
+// 2, the shape geometry's (KArgs::grad_geom), zeroed here
+template <int EW, int FNSET, int GP = 0, class R>
 CX_DEV void run_wave_backward(const KArgs& a, const Ctx& c, Tile<EW> t, int env0, const R& run) {
   run(PH_ADJ, [&](int l) {
-    if (GP) gpar_zero<EW>(a, c, env0, l);
+    if (GP != 0 && gpar_on<GP>(a)) gpar_zero<EW>(a, c, env0, l);
+    if (GP == 2) ggeo_zero<EW>(a, c, env0, l);
     ws_poly_init<EW>(c, t, l);
     ph_geo<EW>(a, c, t, env0, l);
     ph_adj_init<EW>(a, c, t, env0, l);

@@ -30,7 +30,7 @@ constexpr size_t LDS_CAP = 160 * 1024;
 // ---------------------------------------------------------------------------
 struct StepKey {  // step_kernel<EW, fnset, mode, spec, gp>
   int fnset, mode, spec;
-  bool gp;
+  int gp;  // the backward's gradient level: 0 none, 1 the body parameters, 2 the shape geometry (cxk::gpar_on)
   int ews;
 };
 struct HelpKey {  // step_help_kernel<fnset, spec, sdefer, l1>
@@ -49,50 +49,58 @@ constexpr StepKey STEP_KERNELS[] = {
     // generic, every tiling: the step program per contact-function set, the
     // other programs (1 rollout forward, 2 backward re-play, 3 eval with a
     // judge / control, 4 tape backward; 5 / 6 below) analytic or full
-    {F_AN, 0, cxk::SPEC_GENERIC, false, EW_ALL},
-    {F_PP, 0, cxk::SPEC_GENERIC, false, EW_ALL},
-    {F_AP, 0, cxk::SPEC_GENERIC, false, EW_ALL},
-    {F_ALL, 0, cxk::SPEC_GENERIC, false, EW_ALL},
-    {F_AN, 1, cxk::SPEC_GENERIC, false, EW_ALL},
-    {F_ALL, 1, cxk::SPEC_GENERIC, false, EW_ALL},
-    {F_AN, 2, cxk::SPEC_GENERIC, false, EW_ALL},
-    {F_ALL, 2, cxk::SPEC_GENERIC, false, EW_ALL},  // polygon scenes (the host rejects circle x polygon contacts)
-    {F_AN, 3, cxk::SPEC_GENERIC, false, EW_ALL},
-    {F_ALL, 3, cxk::SPEC_GENERIC, false, EW_ALL},
-    {F_AN, 4, cxk::SPEC_GENERIC, false, EW_ALL},
-    {F_ALL, 4, cxk::SPEC_GENERIC, false, EW_ALL},
+    {F_AN, 0, cxk::SPEC_GENERIC, 0, EW_ALL},
+    {F_PP, 0, cxk::SPEC_GENERIC, 0, EW_ALL},
+    {F_AP, 0, cxk::SPEC_GENERIC, 0, EW_ALL},
+    {F_ALL, 0, cxk::SPEC_GENERIC, 0, EW_ALL},
+    {F_AN, 1, cxk::SPEC_GENERIC, 0, EW_ALL},
+    {F_ALL, 1, cxk::SPEC_GENERIC, 0, EW_ALL},
+    {F_AN, 2, cxk::SPEC_GENERIC, 0, EW_ALL},
+    {F_ALL, 2, cxk::SPEC_GENERIC, 0, EW_ALL},  // polygon scenes (the host rejects circle x polygon contacts)
+    {F_AN, 3, cxk::SPEC_GENERIC, 0, EW_ALL},
+    {F_ALL, 3, cxk::SPEC_GENERIC, 0, EW_ALL},
+    {F_AN, 4, cxk::SPEC_GENERIC, 0, EW_ALL},
+    {F_ALL, 4, cxk::SPEC_GENERIC, 0, EW_ALL},
     // the backward with the body parameters' gradient (KArgs::grad_params)
-    {F_AN, 2, cxk::SPEC_GENERIC, true, EW_ALL},
-    {F_ALL, 2, cxk::SPEC_GENERIC, true, EW_ALL},
-    {F_AN, 4, cxk::SPEC_GENERIC, true, EW_ALL},
-    {F_ALL, 4, cxk::SPEC_GENERIC, true, EW_ALL},
+    {F_AN, 2, cxk::SPEC_GENERIC, 1, EW_ALL},
+    {F_ALL, 2, cxk::SPEC_GENERIC, 1, EW_ALL},
+    {F_AN, 4, cxk::SPEC_GENERIC, 1, EW_ALL},
+    {F_ALL, 4, cxk::SPEC_GENERIC, 1, EW_ALL},
+    // the backward with the shape geometry's gradient (KArgs::grad_geom; with
+    // the parameters' where both are asked for).  Generic only: the analytic
+    // scenes' register chain is selected by the body count inside phase G
+    // 
+    {F_AN, 2, cxk::SPEC_GENERIC, 2, EW_ALL},
+    {F_ALL, 2, cxk::SPEC_GENERIC, 2, EW_ALL},
+    {F_AN, 4, cxk::SPEC_GENERIC, 2, EW_ALL},
+    {F_ALL, 4, cxk::SPEC_GENERIC, 2, EW_ALL},
     // the differentiable eval: the eval that also saves (5) and its tape backward (6)
-    {F_AN, 5, cxk::SPEC_GENERIC, false, EW_ALL},
-    {F_ALL, 5, cxk::SPEC_GENERIC, false, EW_ALL},
-    {F_AN, 6, cxk::SPEC_GENERIC, false, EW_ALL},
-    {F_ALL, 6, cxk::SPEC_GENERIC, false, EW_ALL},
+    {F_AN, 5, cxk::SPEC_GENERIC, 0, EW_ALL},
+    {F_ALL, 5, cxk::SPEC_GENERIC, 0, EW_ALL},
+    {F_AN, 6, cxk::SPEC_GENERIC, 0, EW_ALL},
+    {F_ALL, 6, cxk::SPEC_GENERIC, 0, EW_ALL},
     // the reference scenes' step programs at 4 and 2 envs per wave, either PRNG layout
-    {F_AN, 0, cxk::SPEC_ROBOCUP, false, 2 | 4},
-    {F_AN, 0, cxk::SPEC_ROBOCUP_PART, false, 2 | 4},
-    {F_PP, 0, cxk::SPEC_LUNAR, false, 2 | 4},
-    {F_PP, 0, cxk::SPEC_LUNAR_PART, false, 2 | 4},
+    {F_AN, 0, cxk::SPEC_ROBOCUP, 0, 2 | 4},
+    {F_AN, 0, cxk::SPEC_ROBOCUP_PART, 0, 2 | 4},
+    {F_PP, 0, cxk::SPEC_LUNAR, 0, 2 | 4},
+    {F_PP, 0, cxk::SPEC_LUNAR_PART, 0, 2 | 4},
     // the default tiling: RoboCup's other programs (the re-play backward,
     // mode 2, is the tape backward's check: generic only) ...
-    {F_AN, 1, cxk::SPEC_ROBOCUP, false, 4},
-    {F_AN, 3, cxk::SPEC_ROBOCUP, false, 4},
-    {F_AN, 4, cxk::SPEC_ROBOCUP, false, 4},
+    {F_AN, 1, cxk::SPEC_ROBOCUP, 0, 4},
+    {F_AN, 3, cxk::SPEC_ROBOCUP, 0, 4},
+    {F_AN, 4, cxk::SPEC_ROBOCUP, 0, 4},
     // ... the box world's step and rollout programs (finite_scene, grad_box) ...
-    {F_AN, 0, cxk::SPEC_BOX, false, 4},
-    {F_AN, 1, cxk::SPEC_BOX, false, 4},
-    {F_AN, 4, cxk::SPEC_BOX, false, 4},
+    {F_AN, 0, cxk::SPEC_BOX, 0, 4},
+    {F_AN, 1, cxk::SPEC_BOX, 0, 4},
+    {F_AN, 4, cxk::SPEC_BOX, 0, 4},
     // ... and their tape backward with the body parameters' gradient
-    {F_AN, 4, cxk::SPEC_ROBOCUP, true, 4},
-    {F_AN, 4, cxk::SPEC_BOX, true, 4},
+    {F_AN, 4, cxk::SPEC_ROBOCUP, 1, 4},
+    {F_AN, 4, cxk::SPEC_BOX, 1, 4},
     // ... and their differentiable eval
-    {F_AN, 5, cxk::SPEC_ROBOCUP, false, 4},
-    {F_AN, 6, cxk::SPEC_ROBOCUP, false, 4},
-    {F_AN, 5, cxk::SPEC_BOX, false, 4},
-    {F_AN, 6, cxk::SPEC_BOX, false, 4},
+    {F_AN, 5, cxk::SPEC_ROBOCUP, 0, 4},
+    {F_AN, 6, cxk::SPEC_ROBOCUP, 0, 4},
+    {F_AN, 5, cxk::SPEC_BOX, 0, 4},
+    {F_AN, 6, cxk::SPEC_BOX, 0, 4},
 };
 // the step program with a key-window helper wave per env group, without and
 // with the level-1 key ring: RoboCup's specialization
@@ -186,7 +194,8 @@ struct LaunchPlan {
   // the key: fnset, mode, spec, gp of step_kernel; fnset, spec, sdefer of the
   // helper forms (l1: the family); nb, spec of bwd_split_kernel
   int fnset, mode, spec, nb;
-  bool gp, sdefer;
+  int gp;  // StepKey::gp
+  bool sdefer;
   unsigned grid, block;
   size_t lds;
   const char* error;  // the launch cannot run (nullptr: it can)
@@ -212,7 +221,7 @@ inline LaunchPlan plan_launch(const cxk::SceneDev& sc, int fnset, Variant v, con
   p.fnset = cxk::launch_fnset(fnset, mode);  // the contact-function program for this scene
   p.mode = mode;
   p.nb = sc.nb;
-  p.gp = a.grad_params != nullptr;
+  p.gp = a.grad_geom != nullptr ? 2 : a.grad_params != nullptr ? 1 : 0;
   // scene specialization (compile-time dimensions; reference scenes, whose
   // tiles always fit WPB to a workgroup)
   const int spec = v.specialize && p.wpb == WPB ? cxk::spec_of(sc) : cxk::SPEC_GENERIC;
@@ -222,9 +231,9 @@ inline LaunchPlan plan_launch(const cxk::SceneDev& sc, int fnset, Variant v, con
   p.block = 2 * WPB * 64;
   // the tape backward at two waves per env group where the scene allows it
   // and two tiles per group fit (the same bits).  A launch that asks for the
-  // body parameters' gradient runs the one-wave mode 4 (DESIGN section 13:
-  // the consumer chain does not carry them)
-  if (mode == 4 && dev.split_bwd_on && !p.gp && p.wpb == WPB && split_bwd_may_run(sc, fnset, p.ew, a) &&
+  // body parameters' or the shape geometry's gradient runs the one-wave mode 4
+  // (the consumer chain does not carry them)
+  if (mode == 4 && dev.split_bwd_on && p.gp == 0 && p.wpb == WPB && split_bwd_may_run(sc, fnset, p.ew, a) &&
       cxk::lds_bytes(sc, 2 * WPB, 4) <= LDS_CAP && compiled(4, split_key(p))) {
     p.family = FAM_SPLIT;
     p.lds = cxk::lds_bytes(sc, 2 * WPB, 4);

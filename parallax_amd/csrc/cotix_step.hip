@@ -338,6 +338,18 @@ int cotix_scene_variant(const cotix_scene* scene, int* envs_per_wave, int* spec)
 }
 
 int cotix_scene_geom_floats(const cotix_scene* scene) { return scene ? scene->host.G : fail("null scene"); }
+int cotix_scene_geom_part_words(const cotix_scene* scene) {
+  return scene ? cxk::geom_part_words(scene->host) : fail("null scene");
+}
+int cotix_scene_part_geom(const cotix_scene* scene, int part, int* offset, int* count) {
+  if (!scene) return fail("null scene");
+  const SceneDev& s = scene->host;
+  if (part < 0 || part >= s.np) return fail("part out of range");
+  const int kind = (int)s.hot[s.o_pkind + part];
+  if (offset) *offset = (int)s.hot[s.o_pgoff + part];
+  if (count) *count = kind == cx::KIND_POLY ? 2 * (int)s.hot[s.o_pn + part] : 4;
+  return 0;
+}
 
 int cotix_scene_info(const cotix_scene* scene, int* n_contacts, int* n_cells, int* n_candidates, int* n_types) {
   if (!scene) return fail("null scene");
@@ -584,6 +596,16 @@ int cotix_rollout_backward_ex2(cotix_scene* scene, const float* saved_dyn, const
                                const uint32_t* tape, const float* geom, int geom_stride, int B, int n_steps, float dt,
                                int stages, const float* action, int action_body, const float* ret_weights,
                                float* grad_action, float* grad_dyn0, float* grad_params, cotix_stream_t stream) {
+  return cotix_rollout_backward_ex3(scene, saved_dyn, saved_keys, tape, geom, geom_stride, B, n_steps, dt, stages,
+                                    action, action_body, ret_weights, grad_action, grad_dyn0, grad_params, nullptr,
+                                    stream);
+}
+
+int cotix_rollout_backward_ex3(cotix_scene* scene, const float* saved_dyn, const uint32_t* saved_keys,
+                               const uint32_t* tape, const float* geom, int geom_stride, int B, int n_steps, float dt,
+                               int stages, const float* action, int action_body, const float* ret_weights,
+                               float* grad_action, float* grad_dyn0, float* grad_params, float* grad_geom,
+                               cotix_stream_t stream) {
   if (check_step_args(scene, saved_dyn, saved_keys, geom, geom_stride, B, n_steps, stages, action, action_body))
     return -1;
   if (!ret_weights) return fail("null argument");
@@ -596,6 +618,9 @@ int cotix_rollout_backward_ex2(cotix_scene* scene, const float* saved_dyn, const
   // a per-env scene reads every env's parameters from its own geometry row
   if (grad_params && scene->host.epar != 0 && (!geom || geom_stride == 0))
     return fail("grad_params of a per-env-parameter scene needs geom with a geom_stride (one row per env)");
+  // ... and its parts' words: the derivative is with respect to env g's own row
+  if (grad_geom && scene->host.epar != 0 && (!geom || geom_stride == 0))
+    return fail("grad_geom of a per-env scene needs geom with a geom_stride (one row per env)");
   if (B == 0 || n_steps == 0) return 0;
   cxk::KArgs ka{};
   ka.dyn = nullptr;
@@ -618,6 +643,7 @@ int cotix_rollout_backward_ex2(cotix_scene* scene, const float* saved_dyn, const
   ka.grad_action = grad_action;
   ka.grad_dyn = grad_dyn0;
   ka.grad_params = grad_params;
+  ka.grad_geom = grad_geom;
   for (int k = 0; k < scene->host.nb * 6; ++k) ka.ret_w[k] = ret_weights[k];
   return launch(scene, ka, tape ? 4 : 2, stream);
 }

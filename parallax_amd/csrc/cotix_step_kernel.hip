@@ -108,10 +108,11 @@ struct PhaseAcc {
 // that also saves (cotix_eval_rollout: run_wave ESAVE), 6: its tape backward
 // (cotix_eval_backward: run_wave_backward_tape EV);
 // SPEC: scene specialization (cxk::SPEC_*, compile-time dimensions);
-// GP (MODE 2 and 4): the backward with the body parameters' gradient
-// (KArgs::grad_params) -- instantiations of their own, so a launch that does
-// not ask for it runs the kernels it ran before
-template <int EW, int FNSET, int MODE, int SPEC = cxk::SPEC_GENERIC, bool GP = false>
+// GP (MODE 2 and 4): the backward with the body parameters' gradient (1,
+// KArgs::grad_params) or the shape geometry's (2, KArgs::grad_geom; with the
+// parameters' where both are given) -- instantiations of their own, so a
+// launch that does not ask for them runs the kernels it ran before
+template <int EW, int FNSET, int MODE, int SPEC = cxk::SPEC_GENERIC, int GP = 0>
 __global__ __launch_bounds__(WPB * 64) void step_kernel(cxk::KArgs a) {
   extern __shared__ uint32_t lds[];
   CXK_STAMP(st0);
@@ -161,7 +162,7 @@ __global__ __launch_bounds__(WPB * 64) void step_kernel(cxk::KArgs a) {
   PhaseAcc pa;
   const WaveRun run = pa.run(lane);
   if (MODE == 6)
-    cxk::run_wave_backward_tape<EW, FNSET, false, true>(a, c, t, env0, run);
+    cxk::run_wave_backward_tape<EW, FNSET, 0, true>(a, c, t, env0, run);
   else if (MODE == 5)
     cxk::run_wave<EW, FNSET, false, true, false, true>(a, c, t, env0, run, true);
   else if (MODE == 4)

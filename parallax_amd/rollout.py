@@ -24,6 +24,12 @@ d (mass, inertia, elasticity, friction_coefficient) of every body and env
 (cotix_rollout_backward_ex2), and rollout(body_params=...) makes them a
 torch.autograd input -- every body leaf is differentiable in the reference
 (cotix/_bodies.py:140-154).
+
+Shape geometry: rollout_backward(want_geom=True) also returns d ret / d the
+parts' geometry words of every env (cotix_rollout_backward_ex3; Circle.radius
+/ position, AABB.lower / upper, AbstractPolygon.vertices,
+cotix/_convex_shapes.py), and rollout(geometry=...) makes World.geometry() a
+torch.autograd input.
 """
 import numpy as np
 import torch
@@ -100,19 +106,32 @@ def trajectory(saved, B):
     return sd.permute(0, 2, 1, 3).reshape(T, nd // 6, 6, nblk * 4)[..., :B].contiguous()
 
 
-def rollout_backward(world, saved, want_dyn0=False, replay=False, want_params=False):
+def rollout_backward(world, saved, want_dyn0=False, replay=False, want_params=False, want_geom=False):
     """d ret / d actions [T, B, 2] (and d ret / d initial state [nb, 6, B]):
     from the forward's tape, or (replay=True, or no tape saved) re-playing
     the forward's steps.  want_params: returns (ga, gd, gp) with gp f32
     [nb, 4, B] = d ret[env] / d (mass, inertia, elasticity,
     friction_coefficient) of every body, summed over the steps; on a
     shared-parameter world every env's derivative with respect to the shared
-    value (sum over envs for a batch objective)."""
+    value (sum over envs for a batch objective).  want_geom: gg f32 [GW, B]
+    = d ret[env] / d word of World.geometry() follows the other outputs --
+    (ga, gd, gg) or (ga, gd, gp, gg); on shared geometry every env's derivative
+    with respect to the shared word, on per-env rows with respect to the env's
+    own."""
     nb, B = len(world.bodies), world.B
     T = saved["actions"].shape[0]
     ga = torch.empty(T, B, 2, device=world.device, dtype=torch.float32)
     gd = torch.empty(nb, 6, B, device=world.device, dtype=torch.float32) if want_dyn0 else None
     tp = None if replay else saved.get("tape")
+    if want_geom:
+        gp = torch.empty(nb, 4, B, device=world.device, dtype=torch.float32) if want_params else None
+        gg = torch.empty(world.scene.geom_part_words, B, device=world.device, dtype=torch.float32)
+        _ffi.check(_ffi.lib.cotix_rollout_backward_ex3(
+            world.scene.handle, _ffi.ptr(saved["dyn"]), _ffi.ptr(saved["keys"]), _ffi.ptr(tp), _ffi.ptr(world.geom),
+            world.geom_stride, B, T, saved["dt"], saved["stages"], _ffi.ptr(saved["actions"]), saved["action_body"],
+            saved["w"].ctypes.data_as(_ffi._P), _ffi.ptr(ga), _ffi.ptr(gd), _ffi.ptr(gp), _ffi.ptr(gg),
+            _ffi.stream_ptr(world.device)), "cotix_rollout_backward_ex3")
+        return (ga, gd, gp, gg) if want_params else (ga, gd, gg)
     if want_params:
         gp = torch.empty(nb, 4, B, device=world.device, dtype=torch.float32)
         _ffi.check(_ffi.lib.cotix_rollout_backward_ex2(
@@ -170,21 +189,40 @@ class _RolloutParams(torch.autograd.Function):
         return ga, gp, None, None, None, None, None
 
 
-def rollout(world, actions, action_body=None, ret_weights=None, dt=1e-2, stages=_ffi.STAGES_ROBOCUP,
-            body_params=None):
-    """R[env] (differentiable w.r.t. actions via torch.autograd); advances
-    `world` by T steps in place.
+class _RolloutGeom(torch.autograd.Function):
+    """The rollout with the shape geometry (and, optionally, the body
+    parameters) as further differentiable inputs."""
 
-    body_params: also differentiable w.r.t. the bodies' (mass, inertia,
-    elasticity, friction_coefficient).  On a per-env-parameter world a
-    [B, n_bodies, 4] tensor, copied into the world's parameter words
-    (World.body_params()) before the forward; its gradient is d ret / d params
-    weighted by the incoming cotangent, as the actions' is.  On a
-    shared-parameter world a [n_bodies, 4] tensor that equals the scene's
-    parameters bit for bit (they are compiled into the scene at creation:
-    ValueError otherwise); its gradient is the sum over the envs."""
-    if body_params is None:
-        return _Rollout.apply(actions, world, action_body, ret_weights, dt, stages)
+    @staticmethod
+    def forward(ctx, actions, body_params, geometry, world, action_body, ret_weights, dt, stages):
+        per_env = world.scene.per_env_params
+        if body_params is not None and per_env:
+            world.body_params().copy_(body_params.detach())
+        world.geometry().copy_(geometry.detach())  # (no scene constant depends on the geometry)
+        ret, saved = rollout_forward(world, actions.detach(), action_body, ret_weights, dt, stages)
+        ctx.world, ctx.saved, ctx.per_env = world, saved, per_env
+        ctx.geom_version = world.geom._version
+        return ret
+
+    @staticmethod
+    def backward(ctx, g_ret):
+        if ctx.world.geom._version != ctx.geom_version:
+            raise RuntimeError("the world's geometry / body parameters changed between rollout() and backward()")
+        want_p, want_g = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        out = rollout_backward(ctx.world, ctx.saved, want_params=want_p, want_geom=want_g)
+        g = g_ret.to(out[0].dtype)
+        ga = out[0] * g[None, :, None]
+        gp = gg = None
+        if want_p:
+            gp = out[2] * g[None, None, :]  # [nb, 4, B]
+            gp = gp.permute(2, 0, 1).contiguous() if ctx.per_env else gp.sum(dim=2)
+        if want_g:
+            gg = out[-1] * g[None, :]  # [GW, B]
+            gg = gg.T.contiguous() if ctx.world.geom.dim() == 2 else gg.sum(dim=1)
+        return ga, gp, gg, None, None, None, None, None
+
+
+def _check_body_params(world, body_params):
     have = world.body_params()
     if tuple(body_params.shape) != tuple(have.shape):
         raise ValueError("body_params must be %s for this world, got %s" % (tuple(have.shape),
@@ -196,4 +234,38 @@ def rollout(world, actions, action_body=None, ret_weights=None, dt=1e-2, stages=
         raise ValueError("body_params of a shared-parameter world must equal the scene's parameters bit for bit "
                          "(World.body_params(): they are compiled into the scene at creation); build the world "
                          "with per-env parameters to vary them")
-    return _RolloutParams.apply(actions, body_params, world, action_body, ret_weights, dt, stages)
+
+
+def rollout(world, actions, action_body=None, ret_weights=None, dt=1e-2, stages=_ffi.STAGES_ROBOCUP,
+            body_params=None, geometry=None):
+    """R[env] (differentiable w.r.t. actions via torch.autograd); advances
+    `world` by T steps in place.
+
+    body_params: also differentiable w.r.t. the bodies' (mass, inertia,
+    elasticity, friction_coefficient).  On a per-env-parameter world a
+    [B, n_bodies, 4] tensor, copied into the world's parameter words
+    (World.body_params()) before the forward; its gradient is d ret / d params
+    weighted by the incoming cotangent, as the actions' is.  On a
+    shared-parameter world a [n_bodies, 4] tensor that equals the scene's
+    parameters bit for bit (they are compiled into the scene at creation:
+    ValueError otherwise); its gradient is the sum over the envs.
+
+    geometry: also differentiable w.r.t. the parts' geometry words: a float32
+    tensor of World.geometry()'s shape on the world's device ([GW], or
+    [B, GW] for per-env rows), copied into ``world.geom`` before the forward
+    (nothing is compiled into the scene, so any values may be given).  Its
+    gradient is d ret / d geometry weighted by the incoming cotangent, [B, GW]
+    on per-env rows and the sum over the envs on shared geometry.  May be
+    given together with body_params."""
+    if body_params is None and geometry is None:
+        return _Rollout.apply(actions, world, action_body, ret_weights, dt, stages)
+    if body_params is not None:
+        _check_body_params(world, body_params)
+    if geometry is None:
+        return _RolloutParams.apply(actions, body_params, world, action_body, ret_weights, dt, stages)
+    have = world.geometry()
+    if tuple(geometry.shape) != tuple(have.shape):
+        raise ValueError("geometry must be %s for this world, got %s" % (tuple(have.shape), tuple(geometry.shape)))
+    if geometry.dtype != torch.float32 or geometry.device != have.device:
+        raise ValueError("geometry must be a float32 tensor on the world's device")
+    return _RolloutGeom.apply(actions, body_params, geometry, world, action_body, ret_weights, dt, stages)

@@ -54,6 +54,8 @@ class Scene:
                                                    ctypes.byref(h)), "cotix_scene_create_ex2")
         self.handle = h
         self.geom_floats = _ffi.lib.cotix_scene_geom_floats(h)
+        # of which the parts' words (without a per-env scene's parameter words): the rows of grad_geom
+        self.geom_part_words = _ffi.lib.cotix_scene_geom_part_words(h)
 
     def info(self):
         import ctypes
@@ -207,6 +209,27 @@ class World:
         if self.scene.per_env_params:
             return self.geom[:, self.geom.shape[1] - 4 * nb:].view(self.B, nb, 4)
         return self.scene.body_params.to(self.device)
+
+    def geometry(self):
+        """The parts' local geometry words as the kernel reads them, in the
+        stored order -- circle (r, cx, cy, pad), AABB (lo.x, lo.y, up.x, up.y),
+        polygon x, y per vertex as uploaded (clockwise), parts in body order:
+        a view of ``world.geom``, [GW] for shared geometry and [B, GW] for
+        per-env rows, without the parameter words of a per-env-parameter
+        scene.  Writes reach the next launch."""
+        return self.geom[..., :self.scene.geom_part_words]
+
+    def part_geometry(self, body, part=0):
+        """The words of part `part` of body `body` in World.geometry() (a view)."""
+        import ctypes
+        parts = self.bodies[body].shape.parts
+        if not 0 <= part < len(parts):
+            raise IndexError("body %d has %d parts" % (body, len(parts)))
+        index = sum(len(b.shape.parts) for b in self.bodies[:body]) + part
+        off, cnt = ctypes.c_int(), ctypes.c_int()
+        _ffi.check(_ffi.lib.cotix_scene_part_geom(self.scene.handle, index, ctypes.byref(off), ctypes.byref(cnt)),
+                   "cotix_scene_part_geom")
+        return self.geom[..., off.value:off.value + cnt.value]
 
     # -- hot path ---------------------------------------------------------
     def step(self, n_steps=1, dt=1e-2, stages=_ffi.STAGES_ROBOCUP, action=None, action_body=0,

@@ -36,8 +36,10 @@ def parse(jobs):
         for ln in err.split("\n"):
             m = re.search(r"Function Name: (\S+)", ln)
             if m:
-                # (a trailing defaulted `false` template argument is the same kernel)
-                cur = "ew%d %s" % (ew, re.sub(r"(step_kernelILi\d+ELi\d+ELi\d+ELi\d+E)Lb0E", r"\1", m.group(1)))
+                # (a trailing defaulted `false` / 0 template argument is the same kernel, and
+                # the gradient level that was a bool is the same kernel at the same value)
+                cur = re.sub(r"(step_kernelILi\d+ELi\d+ELi\d+ELi\d+E)L[bi]0E", r"\1", m.group(1))
+                cur = "ew%d %s" % (ew, re.sub(r"(step_kernelILi\d+ELi\d+ELi\d+ELi\d+E)Lb1E", r"\1Li1E", cur))
                 rows[cur] = {}
                 continue
             m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", ln)
