@@ -586,6 +586,59 @@ extern "C" int emu_launch_plan(void* scene, int envs_per_wave, int specialize, i
   return 14;
 }
 
+// the kernel list (cxl::STEP_KERNELS / HELP_KERNELS / SPLIT_KERNELS) as rows
+// of 5 ints, `which` 0 / 1 / 2: step (fnset, mode, spec, gp, ews), help
+// (fnset, spec, sdefer, l1, ews), split (nb, spec, 0, 0, ews).  Returns the
+// list's length; writes at most `cap` rows
+extern "C" int emu_kernel_list(int which, int* out, int cap) {
+  int n = 0;
+  auto put = [&](int a, int b, int c, int d, int ews) {
+    if (n < cap) {
+      const int v[5] = {a, b, c, d, ews};
+      for (int k = 0; k < 5; ++k) out[5 * n + k] = v[k];
+    }
+    ++n;
+  };
+  if (which == 0)
+    for (const cxl::StepKey& k : cxl::STEP_KERNELS) put(k.fnset, k.mode, k.spec, k.gp, k.ews);
+  else if (which == 1)
+    for (const cxl::HelpKey& k : cxl::HELP_KERNELS) put(k.fnset, k.spec, k.sdefer, k.l1, k.ews);
+  else if (which == 2)
+    for (const cxl::SplitKey& k : cxl::SPLIT_KERNELS) put(k.nb, k.spec, 0, 0, k.ews);
+  else
+    return -1;
+  return n;
+}
+
+// emu_launch_plan for every program of the library (modes 0 .. 6) and either
+// gradient request, with the arguments as the library's entry points set them
+// (cotix_step.hip): the backwards (2, 4, 6) without the broadphase stage, the
+// tape where the launch carries one (1, 4, 5, 6).  The same 14 words
+extern "C" int emu_launch_plan_ex(void* scene, int envs_per_wave, int specialize, int mode, int B, int n_steps,
+                                  int stages, int grad_params, int grad_geom, int cus, int key_helper_on,
+                                  int split_bwd_on, long* out) {
+  const EmuScene* s = static_cast<EmuScene*>(scene);
+  if (mode < 0 || mode > 6) return -1;
+  static uint32_t tape;  // (never read: the plan looks at the pointers only)
+  static float gp, gg;
+  cxk::KArgs a{};
+  a.B = B;
+  a.n_steps = n_steps;
+  a.stages = mode == 2 || mode == 4 || mode == 6 ? stages & ~COTIX_STAGE_BROADPHASE : stages;
+  a.tape = mode == 1 || mode >= 4 ? &tape : nullptr;
+  a.grad_params = grad_params ? &gp : nullptr;
+  a.grad_geom = grad_geom ? &gg : nullptr;
+  const cxl::LaunchPlan p = cxl::plan_launch(s->s, s->fnset, {envs_per_wave, specialize}, a, mode,
+                                             cxl::Device{cus, key_helper_on != 0, split_bwd_on != 0});
+  const bool listed = p.family == cxl::FAM_STEP    ? cxl::compiled(p.ew, cxl::step_key(p))
+                      : p.family == cxl::FAM_SPLIT ? cxl::compiled(p.ew, cxl::split_key(p))
+                                                   : cxl::compiled(p.ew, cxl::help_key(p));
+  const long v[] = {p.family, p.ew,    p.wpb,  p.fnset,     p.mode,      p.spec,      p.gp,
+                    p.sdefer, p.nb,    p.grid, p.block, (long)p.lds, p.error != nullptr, listed};
+  for (int k = 0; k < 14; ++k) out[k] = v[k];
+  return 14;
+}
+
 // circle x polygon: the gradient's recorded re-run (cx::cp_forward) against
 // the forward contact (cx::circle_vs_polygon) -- same penetration bits
 extern "C" int emu_circle_poly_check(int n, const float* a, const float* b, float* pen_fwd, float* pen_rec) {

@@ -2,7 +2,11 @@
 launch runs, through the host emulation's emu_launch_plan.  The expected rows
 are literals written from the launcher the plan replaced (its launch(), the
 two form launchers and the per-tiling ladder), and every plan over the cross
-product of scenes, variants and launch arguments names a kernel of the list."""
+product of scenes, variants and launch arguments names a kernel of the list --
+the differentiable eval's programs (modes 5 / 6) and the backward with the
+shape geometry's gradient (gp 2) included, through emu_launch_plan_ex.  Which
+row of tests/kernel_matrix.py runs each kernel of the list is
+tests/test_kernel_matrix_cpu.py's."""
 import ctypes
 import itertools
 import os
@@ -35,6 +39,7 @@ def planner():
     from cotix_oracle.params import Params
     lib = emu.load()
     lib.emu_launch_plan.argtypes = [ctypes.c_void_p] + [ctypes.c_int] * 10 + [ctypes.POINTER(ctypes.c_long)]
+    lib.emu_launch_plan_ex.argtypes = [ctypes.c_void_p] + [ctypes.c_int] * 11 + [ctypes.POINTER(ctypes.c_long)]
     lib.emu_lds_bytes_w.restype = ctypes.c_long
     lib.emu_lds_bytes_w.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
     part = Params(prng_layout="partitionable")
@@ -58,6 +63,15 @@ def planner():
         assert n == len(FIELDS)
         return dict(zip(FIELDS, out))
 
+    def plan_ex(scene, ew, specialize, mode, B, n_steps, collider, gp, cus, key_helper, split_bwd):
+        """Every program (modes 0 .. 6) at gradient level gp 0, 1 or 2."""
+        n = lib.emu_launch_plan_ex(scenes[scene], ew, specialize, mode, B, n_steps,
+                                   ADVANCE | (COLLIDER if collider else 0), int(gp >= 1), int(gp == 2), cus,
+                                   int(key_helper), int(split_bwd), out)
+        assert n == len(FIELDS)
+        return dict(zip(FIELDS, out))
+
+    plan.ex = plan_ex
     plan.lds = lambda scene, ew, wpb: lib.emu_lds_bytes_w(scenes[scene], ew, wpb)
     plan.scenes = tuple(scenes)
     return plan
@@ -178,3 +192,23 @@ def test_every_plan_is_in_the_kernel_list(planner):
                 assert p["listed"] == 1 or p["error"] == 1, (scene, ew, specialize, mode, gp, n_steps, B, cus, kh, sb)
                 n += not p["error"]
     assert n > 100000
+    # ... the differentiable eval's programs (5, 6) and the gradient levels 0,
+    # 1 (the body parameters) and 2 (the shape geometry) of the backwards
+    # included, and the plan says what was asked for
+    m = 0
+    for scene in planner.scenes:
+        for ew, specialize, mode, gp in itertools.product((1, 2, 4, 8), (0, 1), range(7), (0, 1, 2)):
+            if gp and mode not in (2, 4):
+                continue
+            for n_steps, B, cus, kh, sb, coll in itertools.product((1, 17), (13, 4096, 4097), (0, 256), (0, 1), (0, 1),
+                                                                   (0, 1)):
+                p = planner.ex(scene, ew, specialize, mode, B, n_steps, bool(coll), gp, cus, kh, sb)
+                what = (scene, ew, specialize, mode, gp, n_steps, B, cus, kh, sb)
+                assert p["listed"] == 1 or p["error"] == 1, what
+                if not p["error"]:
+                    assert (p["ew"], p["gp"]) == (ew, gp) and (p["family"] != STEP or p["mode"] == mode), what
+                    if mode <= 4 and gp <= 1:  # the older query plans the same launch
+                        q = planner(scene, ew, specialize, mode, B, n_steps, bool(coll), bool(gp), cus, kh, sb)
+                        assert all(p[f] == q[f] for f in FIELDS), what
+                m += not p["error"]
+    assert m > 30000
