@@ -60,21 +60,51 @@ static float cos_poly(float r) {
   float z = r * r;
   return ((((2.443315711809948e-5f * z + -1.388731625493765e-3f) * z + 4.166664568298827e-2f) * z) * z - 0.5f * z) + 1.0f;
 }
+/* finite |x| > 8192: x * 2/pi mod 4 from the significand and the 96 bits of
+ * 2/pi that the exponent selects (geometry._reduce_large has the derivation);
+ * returns r in [-pi/4, pi/4] and the quadrant */
+static const uint32_t TWO_OVER_PI[8] = {0x00000000u, 0xA2F9836Eu, 0x4E441529u, 0xFC2757D1u,
+                                        0xF534DDC0u, 0xDB629599u, 0x3C439041u, 0xFE5163ABu};
+static float reduce_large(float x, int* qo) {
+  uint32_t u; memcpy(&u, &x, 4);
+  uint64_t m = (u & 0x007FFFFFu) | 0x00800000u;
+  uint32_t u0 = ((u >> 23) & 0xFFu) - 120u, n = u0 >> 5, sh = 32u - (u0 & 31u);
+  uint64_t w[3];
+  for (int i = 0; i < 3; ++i) w[i] = (uint32_t)((((uint64_t)TWO_OVER_PI[n + i] << 32) | TWO_OVER_PI[n + i + 1]) >> sh);
+  uint64_t hi = ((m * w[0]) << 32) + m * w[1] + ((m * w[2]) >> 32);
+  uint32_t q = (uint32_t)((hi + (1ull << 61)) >> 62);
+  uint64_t fr = hi << 2;
+  double d = (double)(int32_t)(uint32_t)(fr >> 32) * 4294967296.0 + (double)(uint32_t)fr;
+  float r = (float)(d * 0x1.921fb54442d18p-64);
+  if (u >> 31) { r = -r; q = 0u - q; }
+  *qo = (int)(q & 3u);
+  return r;
+}
 static void sincos32(float x, float* so, float* co) {
   if (isn(x) || isinf(x)) { *so = qnan(); *co = qnan(); return; }
-  float t = x * 0.636619772367581343f;
-  float k = (t + 12582912.0f) - 12582912.0f;
-  float r = ((x - k * 1.5703125f) - k * 4.837512969970703125e-4f) - k * 7.54978995489188216e-8f;
+  float r; int q;
+  if (fabsf(x) > 8192.0f) r = reduce_large(x, &q);
+  else {
+    float t = x * 0.636619772367581343f;
+    float k = (t + 12582912.0f) - 12582912.0f;  /* |k| <= 5216 */
+    r = ((x - k * 1.5703125f) - k * 4.837512969970703125e-4f) - k * 7.54978995489188216e-8f;
+    q = ((int)k) & 3;
+  }
   float s = sin_poly(r), c = cos_poly(r);
-  int q = ((int)k) & 3;
   if (q == 0) { *so = s; *co = c; } else if (q == 1) { *so = c; *co = -s; }
   else if (q == 2) { *so = -s; *co = -c; } else { *so = -c; *co = s; }
 }
-static float atan01(float t) {
-  float y0 = 0.0f;
-  if (t > 0.4142135623730950f) { y0 = 0.785398163397448309616f; t = (t - 1.0f) / (t + 1.0f); }
+/* three intervals: the polynomial alone up to tan(pi/8), about atan(1/2) up to 0.6, about pi/4 beyond;
+ * constants as hi + lo; sw: the caller returns pi/2 - this, whose lo is folded in (geometry._atan01) */
+static float atan01(float t, int sw) {
+  float y0 = 0.0f, lo = 0.0f;
+  if (t > 0.6f) { y0 = 0.785398163397448309616f; lo = sw ? 2.185569414e-8f : -2.185569414e-8f; t = (t - 1.0f) / (t + 1.0f); }
+  else if (t > 0.4142135623730950f) {
+    y0 = 0.4636476039886474609375f; lo = sw ? 4.872354964e-8f : 5.012158688e-9f; t = (t - 0.5f) / (0.5f * t + 1.0f);
+  }
   float z = t * t;
-  return y0 + (((((8.05374449538e-2f * z + -1.38776856032e-1f) * z + 1.99777106478e-1f) * z + -3.33329491539e-1f) * z) * t + t);
+  float p = ((((8.05374449538e-2f * z + -1.38776856032e-1f) * z + 1.99777106478e-1f) * z + -3.33329491539e-1f) * z) * t;
+  return y0 + ((p + lo) + t);
 }
 static float atan2_32(float y, float x) {
   const float PI = 3.14159265358979323846f, PIO2 = 1.57079632679489661923f;
@@ -85,7 +115,7 @@ static float atan2_32(float y, float x) {
   }
   if (x == 0.0f) return y < 0.0f ? -PIO2 : PIO2;
   float ax = fabsf(x), ay = fabsf(y);
-  float r = (ay <= ax) ? atan01(ay / ax) : (PIO2 - atan01(ax / ay));
+  float r = (ay <= ax) ? atan01(ay / ax, 0) : (PIO2 - atan01(ax / ay, 1));
   if (x < 0.0f) r = PI - r;
   return y < 0.0f ? -r : r;
 }
@@ -794,5 +824,14 @@ int oracle_epa(int n, const float* a, const float* b, const float* simplex, int 
     V2 p = epa(&A, &Bs, s, iters);
     pen[2 * i] = p.x; pen[2 * i + 1] = p.y;
   }
+  return 0;
+}
+/* the transcendentals themselves (tests/test_transcendentals_cpu.py) */
+int oracle_sincos(const float* x, int n, float* s, float* c) {
+  for (int i = 0; i < n; ++i) sincos32(x[i], &s[i], &c[i]);
+  return 0;
+}
+int oracle_atan2(const float* y, const float* x, int n, float* out) {
+  for (int i = 0; i < n; ++i) out[i] = atan2_32(y[i], x[i]);
   return 0;
 }

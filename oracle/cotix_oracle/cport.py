@@ -34,6 +34,8 @@ def load():
     lib.oracle_epa.argtypes = [ctypes.c_int, _P, _P, _P, ctypes.c_int, _P]
     lib.oracle_rollout.argtypes = [_P, _P, _P, _P, _P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float,
                                    ctypes.c_int, _P, ctypes.c_int, _P, _P, ctypes.c_int]
+    lib.oracle_sincos.argtypes = [_P, ctypes.c_int, _P, _P]
+    lib.oracle_atan2.argtypes = [_P, _P, ctypes.c_int, _P]
     return lib
 
 

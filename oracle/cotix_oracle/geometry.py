@@ -161,19 +161,62 @@ def _cos_poly(r):
     return ((((_C0 * z + _C1) * z + _C2) * z) * z - F(0.5) * z) + ONE
 
 
+# The first 224 bits of 2/pi after the binary point, below 32 zero bits (the
+# integer part and 31 more, so that every window starts inside the table), as
+# 32-bit words, most significant first.  Derivation (mpmath, 400 bits):
+#   z = int(mpmath.floor(2 / mpmath.pi * 2**224))
+#   words = [0] + [(z >> (32 * (6 - i))) & 0xFFFFFFFF for i in range(7)]
+# tests/test_transcendentals_cpu.py recomputes it.
+TWO_OVER_PI_WORDS = (0x00000000, 0xA2F9836E, 0x4E441529, 0xFC2757D1,
+                     0xF534DDC0, 0xDB629599, 0x3C439041, 0xFE5163AB)
+_TWO_OVER_PI_BITS = sum(w << (32 * (7 - i)) for i, w in enumerate(TWO_OVER_PI_WORDS))  # 2/pi * 2**224, truncated
+_PIO2_64 = float.fromhex("0x1.921fb54442d18p-64")  # f64(pi/2) * 2**-64
+SINCOS_SMALL_MAX = F(8192.0)
+
+
+def _reduce_large(x):
+    """(r, quadrant) of a finite float32 |x| > 8192, Payne-Hanek style.
+    x = +-m * 2**e with the 24-bit integer m.  x * 2/pi mod 4 needs no bit of
+    2/pi of weight 2**-p with p <= e - 2 (m times it is a multiple of 4), so
+    take the 96 bits from p = e - 1 on, as the integer P: m * P mod 2**96 is
+    x * 2/pi mod 4 in units of 2**-94, short by less than 2**-70 (the bits of
+    2/pi past the window).  Its top 64 bits: 2 of quadrant, 62 of fraction.
+    Rounding the fraction to nearest leaves the signed fr / 2**64 in
+    [-1/2, 1/2); r = f32(f64(fr) * f64(pi/2) * 2**-64).  A negative x takes
+    the opposite quadrant and -r."""
+    u = int(F(x).view(np.uint32))
+    m = (u & 0x007FFFFF) | 0x00800000
+    e = ((u >> 23) & 0xFF) - 150
+    first = (e - 1) + 31  # index, from the top of the 256-bit table, of the bit of weight 2**-(e - 1)
+    P = (_TWO_OVER_PI_BITS >> (256 - 96 - first)) & ((1 << 96) - 1)
+    hi = ((m * P) & ((1 << 96) - 1)) >> 32
+    q = ((hi + (1 << 61)) >> 62) & 3
+    fr = (hi << 2) & ((1 << 64) - 1)
+    if fr >= 1 << 63:
+        fr -= 1 << 64
+    r = F(np.float64(float(fr)) * np.float64(_PIO2_64))  # float(int) rounds to nearest even
+    if u >> 31:
+        return -r, (-q) & 3
+    return r, q
+
+
 def sincos32(x):
-    """Returns (sin x, cos x) in float32.  Quadrant k = rint(x*2/pi) by the
-    1.5*2^23 trick, r = ((x - k*P1) - k*P2) - k*P3, cephes polynomials on
-    |r| <= pi/4."""
+    """Returns (sin x, cos x) in float32, for every finite x.  |x| <= 8192:
+    quadrant k = rint(x*2/pi) by the 1.5*2^23 trick (|k| <= 5216, k * P1
+    exact), r = ((x - k*P1) - k*P2) - k*P3; beyond, _reduce_large.  Cephes
+    polynomials on |r| <= pi/4."""
     x = F(x)
     if isnan(x) or np.isinf(x):
         return NAN, NAN
-    t = x * _TWO_OVER_PI
-    k = (t + _MAGIC) - _MAGIC
-    r = ((x - k * _PIO2_1) - k * _PIO2_2) - k * _PIO2_3
+    if abs(x) > SINCOS_SMALL_MAX:
+        r, q = _reduce_large(x)
+    else:
+        t = x * _TWO_OVER_PI
+        k = (t + _MAGIC) - _MAGIC
+        r = ((x - k * _PIO2_1) - k * _PIO2_2) - k * _PIO2_3
+        q = int(k) & 3
     s = _sin_poly(r)
     c = _cos_poly(r)
-    q = int(k) & 3
     if q == 0:
         return s, c
     if q == 1:
@@ -183,16 +226,34 @@ def sincos32(x):
     return -c, s
 
 
-def _atan01(t):
-    """cephes atanf on t in [0, 1]."""
-    if t > _TP8:
+_ATAN_HALF = F(0.4636476039886474609375)
+# the constants' low parts (mpmath: c - float32(c)), alone and less pi/2's own
+_PIO4_LO, _PIO4_LO_SW = F(-2.185569414e-8), F(2.185569414e-8)
+_ATAN_HALF_LO, _ATAN_HALF_LO_SW = F(5.012158688e-9), F(4.872354964e-8)
+
+
+def _atan01(t, swapped=False):
+    """atan on t in [0, 1] with the cephes atanf polynomial, in three
+    intervals (cephes has two): t <= tan(pi/8) directly; t <= 0.6 about
+    atan(1/2), u = (t - 1/2) / (1 + t/2); beyond about pi/4,
+    u = (t - 1) / (t + 1).  With pi/4 alone a result in [0.39, 0.5) is the
+    difference of two numbers of twice its ulp, and came out up to 3.2 ulp
+    off.  The constants are split hi + lo and lo joins the sum before it is
+    rounded; swapped: the caller returns pi/2 - this, and pi/2's lo is
+    folded in here."""
+    y0 = ZERO
+    lo = ZERO
+    if t > F(0.6):
         y0 = PIO4_F
+        lo = _PIO4_LO_SW if swapped else _PIO4_LO
         t = (t - ONE) / (t + ONE)
-    else:
-        y0 = ZERO
+    elif t > _TP8:
+        y0 = _ATAN_HALF
+        lo = _ATAN_HALF_LO_SW if swapped else _ATAN_HALF_LO
+        t = (t - F(0.5)) / (F(0.5) * t + ONE)
     z = t * t
-    p = ((((_A0 * z + _A1) * z + _A2) * z + _A3) * z) * t + t
-    return y0 + p
+    p = ((((_A0 * z + _A1) * z + _A2) * z + _A3) * z) * t
+    return y0 + ((p + lo) + t)
 
 
 def atan2_32(y, x):
@@ -211,7 +272,7 @@ def atan2_32(y, x):
     if ay <= ax:
         r = _atan01(ay / ax)
     else:
-        r = PIO2_F - _atan01(ax / ay)
+        r = PIO2_F - _atan01(ax / ay, True)
     if x < ZERO:
         r = PI_F - r
     return -r if y < ZERO else r

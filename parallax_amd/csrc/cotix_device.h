@@ -89,17 +89,65 @@ CX_DEV float cos_poly(float r) {
           0.5f * z) +
          1.0f;
 }
+// Argument reduction of a finite |x| > 8192 (Payne-Hanek, integers only up to
+// the last step; the oracle's geometry._reduce_large states the same with
+// Python integers and notes where the table comes from).  x = +-m * 2^e with
+// the 24-bit integer significand m; a bit of 2/pi of weight 2^-p adds a
+// multiple of 4 to x * 2/pi when p <= e - 2, so the 96 bits of 2/pi from
+// p = e - 1 on (three words w0 w1 w2 of the table, whose first word is the 32
+// zero bits above the binary point) give x * 2/pi mod 4 to 2^-62: the top two
+// bits of `hi` are the quadrant, the next 62 the fraction.  Rounded to
+// nearest, the fraction is the signed `fr` / 2^64 in [-1/2, 1/2), and
+// r = fr * (pi/2) / 2^64 (one exact int64 -> f64 conversion's rounding, one
+// f64 product, one rounding to f32).  Out of line: a cold path that no
+// benchmarked workload takes stays out of the hot kernels' live ranges.
+#if defined(__HIP__) || defined(__HIPCC__)
+static __device__ __noinline__
+#else
+static
+#endif
+uint64_t sincos_reduce_large(float x) {  // r's bits | quadrant << 32: returned in registers
+  const uint32_t TWO_OVER_PI[8] = {0x00000000u, 0xA2F9836Eu, 0x4E441529u, 0xFC2757D1u,
+                                   0xF534DDC0u, 0xDB629599u, 0x3C439041u, 0xFE5163ABu};
+  const uint32_t u = __float_as_uint(x);
+  const uint64_t m = (uint64_t)((u & 0x007FFFFFu) | 0x00800000u);
+  const uint32_t u0 = ((u >> 23) & 0xFFu) - 120u;  // first table bit used; biased exponent 141 .. 254: 21 .. 134
+  const uint32_t n = u0 >> 5, sh = 32u - (u0 & 31u);  // sh in 1 .. 32
+  const uint64_t w0 = (uint32_t)((((uint64_t)TWO_OVER_PI[n] << 32) | TWO_OVER_PI[n + 1]) >> sh);
+  const uint64_t w1 = (uint32_t)((((uint64_t)TWO_OVER_PI[n + 1] << 32) | TWO_OVER_PI[n + 2]) >> sh);
+  const uint64_t w2 = (uint32_t)((((uint64_t)TWO_OVER_PI[n + 2] << 32) | TWO_OVER_PI[n + 3]) >> sh);
+  const uint64_t hi = ((m * w0) << 32) + m * w1 + ((m * w2) >> 32);  // (m * w0w1w2 mod 2^96) >> 32
+  const uint32_t q = (uint32_t)((hi + (1ull << 61)) >> 62);          // quadrant, fraction rounded to nearest
+  const uint64_t fr = hi << 2;                                       // two's complement fraction * 2^64
+  const int32_t fh = (int32_t)(uint32_t)(fr >> 32);
+  const double d = (double)fh * 4294967296.0 + (double)(uint32_t)fr;  // == (double)(int64_t)fr, one rounding
+  const float r = (float)(d * 0x1.921fb54442d18p-64);
+  // sin(-x) = -sin x, cos(-x) = cos x: the opposite quadrant and fraction
+  const bool ng = (u >> 31) != 0u;
+  return (uint64_t)__float_as_uint(ng ? -r : r) | ((uint64_t)((ng ? 0u - q : q) & 3u) << 32);
+}
 // (the kernels below are written as flat selects: their branchy forms
 // compile to divergent branches on gfx950; every value is computed by the
 // same expression as the branchy form, so the results are identical)
 CX_DEV void sincos32(float x, float* s_out, float* c_out) {
   const bool bad = isn(x) || __builtin_isinf(x);
   const float xs = bad ? 0.0f : x;
-  float t = xs * 0.636619772367581343f;
+  // |x| <= 8192: three-constant Cody-Waite, exact while k * 1.5703125f is
+  // (|k| <= 5216, so (int)k is defined); a larger finite |x| takes the one
+  // branch of this function, uniformly not taken by every rollout whose
+  // bodies have not spun that far
+  const bool big = __builtin_fabsf(xs) > 8192.0f;
+  const float xm = big ? 0.0f : xs;
+  float t = xm * 0.636619772367581343f;
   float k = (t + 12582912.0f) - 12582912.0f;
-  float r = ((xs - k * 1.5703125f) - k * 4.837512969970703125e-4f) - k * 7.54978995489188216e-8f;
-  float s = sin_poly(r), c = cos_poly(r);
+  float r = ((xm - k * 1.5703125f) - k * 4.837512969970703125e-4f) - k * 7.54978995489188216e-8f;
   int q = ((int)k) & 3;
+  if (__builtin_expect(big, 0)) {
+    const uint64_t rq = sincos_reduce_large(xs);
+    r = __uint_as_float((uint32_t)rq);
+    q = (int)(rq >> 32);
+  }
+  float s = sin_poly(r), c = cos_poly(r);
   // q = 0: (s, c), 1: (c, -s), 2: (-s, -c), 3: (-c, s)
   float so = (q & 1) ? c : s, co = (q & 1) ? -s : c;
   so = (q & 2) ? -so : so;
@@ -107,19 +155,31 @@ CX_DEV void sincos32(float x, float* s_out, float* c_out) {
   *s_out = bad ? qnan() : so;
   *c_out = bad ? qnan() : co;
 }
-CX_DEV float atan01(float t) {
-  const bool big = t > 0.4142135623730950f;
-  const float y0 = big ? 0.785398163397448309616f : 0.0f;
-  t = big ? (t - 1.0f) / (t + 1.0f) : t;
+// atan on [0, 1] in three intervals (cephes atanf has two): t <= tan(pi/8)
+// by the polynomial alone; up to 0.6 about atan(1/2), u = (t - 1/2) / (1 + t/2);
+// beyond about pi/4, u = (t - 1) / (t + 1).  Both numerators are exact.  With
+// pi/4 alone a result in [0.39, 0.5) came 3.2 ulp off: it is the difference of
+// two numbers of twice its ulp.  Each constant is added as hi + lo, lo before
+// the rounding of the sum; sw: the caller returns pi/2 - this, and pi/2's own
+// lo goes in here, where it is not rounded away.
+CX_DEV float atan01(float t, bool sw) {
+  const bool mid = t > 0.4142135623730950f, big = t > 0.6f;
+  const float y0 = big ? 0.785398163397448309616f : (mid ? 0.4636476039886474609375f : 0.0f);
+  const float lo_big = sw ? 2.185569414e-8f : -2.185569414e-8f;  // lo(pi/4) [- lo(pi/2)]
+  const float lo_mid = sw ? 4.872354964e-8f : 5.012158688e-9f;   // lo(atan(1/2)) [- lo(pi/2)]
+  const float lo = big ? lo_big : (mid ? lo_mid : 0.0f);
+  const float num = big ? t - 1.0f : (mid ? t - 0.5f : t);
+  const float den = big ? t + 1.0f : (mid ? 0.5f * t + 1.0f : 1.0f);
+  t = num / den;
   float z = t * t;
-  float p = ((((8.05374449538e-2f * z + -1.38776856032e-1f) * z + 1.99777106478e-1f) * z + -3.33329491539e-1f) * z) * t + t;
-  return y0 + p;
+  float p = ((((8.05374449538e-2f * z + -1.38776856032e-1f) * z + 1.99777106478e-1f) * z + -3.33329491539e-1f) * z) * t;
+  return y0 + ((p + lo) + t);
 }
 CX_DEV float atan2_32(float y, float x) {
   const float PI = 3.14159265358979323846f, PIO2 = 1.57079632679489661923f;
   const float ax = __builtin_fabsf(x), ay = __builtin_fabsf(y);
   const bool sw = !(ay <= ax);  // (ay <= ax) ? atan01(ay / ax) : PIO2 - atan01(ax / ay)
-  float r = atan01((sw ? ax : ay) / (sw ? ay : ax));
+  float r = atan01((sw ? ax : ay) / (sw ? ay : ax), sw);
   r = sw ? PIO2 - r : r;
   r = x < 0.0f ? PI - r : r;
   r = y < 0.0f ? -r : r;

@@ -324,6 +324,10 @@ def _edge_floats(rng, n):
     special = np.array([0.0, -0.0, np.inf, -np.inf, np.nan, 1e-45, -1e-45, 1e-38, np.pi, -np.pi, np.pi / 2,
                         -np.pi / 2, np.pi / 4, 3 * np.pi / 4, 1e4, -1e4, 0.41421356, 0.41421357, 1.0, -1.0],
                        np.float32)
+    # beyond sincos32's 8192 seam: its exact reduction, up to where a float -> int quadrant would be undefined
+    large = np.array([8192.0, 8192.0009765625, -8192.0009765625, 3.0e4, -1.0e6, 6.6e6, 7.0e6, -1.0e7, 3.3731974e9,
+                      4.0e9, -1.0e20, 3.0e38, np.finfo(np.float32).max, -np.finfo(np.float32).max], np.float32)
+    special = np.concatenate([special, large])
     return np.concatenate([special, rng.normal(0, 3, n).astype(np.float32),
                            rng.uniform(-1e3, 1e3, n).astype(np.float32)])
 

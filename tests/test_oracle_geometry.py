@@ -104,15 +104,21 @@ def test_order_clockwise_consistency():
 
 
 def test_sincos_atan2_accuracy():
-    xs = np.linspace(-50, 50, 2001).astype(F)
+    """sin / cos within 2^-23 of float64's and within 2^-22 of the unit circle,
+    atan2 within 2 ulp of float64's rounded to float32 (the whole float32
+    range: tests/test_transcendentals_cpu.py)."""
+    xs = np.concatenate([np.linspace(-50, 50, 2001), np.linspace(8000, 8400, 401), [3.0e4, -1.0e7, 4.0e9]]).astype(F)
     for x in xs:
         s, c = G.sincos32(x)
-        assert abs(float(s) - np.sin(np.float64(x))) < 4e-7
-        assert abs(float(c) - np.cos(np.float64(x))) < 4e-7
+        assert abs(float(s) - np.sin(np.float64(x))) <= 2.0 ** -23
+        assert abs(float(c) - np.cos(np.float64(x))) <= 2.0 ** -23
+        assert abs(float(s) ** 2 + float(c) ** 2 - 1.0) <= 2.0 ** -22
     rng = np.random.default_rng(3)
     for _ in range(2000):
         y, x = (F(v) for v in rng.normal(size=2) * 10)
-        assert abs(float(G.atan2_32(y, x)) - np.arctan2(np.float64(y), np.float64(x))) < 6e-7
+        ref = np.arctan2(np.float64(y), np.float64(x))
+        assert abs(float(G.atan2_32(y, x)) - ref) <= 2 * float(np.spacing(abs(F(ref))))
+        assert abs(float(G.atan2_32(y, x)) - ref) < 6e-7
     for y, x in [(0.0, 1.0), (-0.0, 1.0), (0.0, -1.0), (-0.0, -1.0), (1.0, 0.0), (-1.0, 0.0)]:
         assert float(G.atan2_32(F(y), F(x))) == pytest.approx(np.arctan2(y, x), abs=1e-7)
         assert np.signbit(G.atan2_32(F(y), F(x))) == np.signbit(np.arctan2(y, x))
