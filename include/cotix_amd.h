@@ -32,6 +32,8 @@
  *   cotix_observe         the observation tensor of env.step()
  *   cotix_render          env.draw(painter) via Painter callbacks  cotix/_viz.py:55-75,
  *                         cotix/_robocup.py:140-150, cotix/_lunar_lander.py:220-225
+ *   cotix_rasterize       env.draw(painter) down to the pixel: u8 image observations
+ *                         of every env (the filled bodies of cotix/_viz.py:55-75)
  *   cotix_check_state     class_invariant  cotix/_design_by_contract.py:80-107
  *   cotix_eval            AbstractEnvironment.eval     cotix/_envs.py:37-132 with a
  *                         device AbstractJudge (:9-28) / AbstractControl
@@ -539,6 +541,36 @@ int cotix_observe(const float* dyn, int n_bodies, int B, float* obs, cotix_strea
 int cotix_render_count(const cotix_scene* scene);
 int cotix_render(const cotix_scene* scene, const float* dyn, const float* geom, int geom_stride, int B, float* prims,
                  cotix_stream_t stream);
+
+/* Pixel observations: every env's filled bodies rasterized in one launch
+ * (DESIGN.md section 16).  The image is width x height pixels, row 0 at the
+ * top; pixel (column i, row j) is the world point
+ *   u = float(2 i + 1 - width) / float(width),  v = float(height - (2 j + 1)) / float(height)
+ *   loc = (cx + u * half_w, cy + v * half_h)
+ *   p   = loc                                   follow_body < 0
+ *       = loc + position of body follow_body    follow_body >= 0, follow_angle == 0
+ *       = HomogenuousTransformer(position, angle of that body).forward_vector(loc)   follow_angle == 1
+ * (one f32 operation at a time, no fused multiply-add) and its id is 1 + b for
+ * the last body b, in scene order, with a part whose world shape contains(p)
+ * -- the reference's Circle / AABB / Polygon.contains, eps included, of the
+ * parts cotix_render exports -- and 0 where no part does.  A NaN pose paints
+ * nothing.  Filled bodies only: no outlines, no lines, no anti-aliasing, no
+ * culling.
+ *   channels == 1: image device u8 [B][height][width], the ids
+ *   channels == 3: image device u8 [B][3][height][width] (planar), plane c of
+ *                  a pixel = palette[3 * id + c]; palette is a HOST array of
+ *                  3 * (n_bodies + 1) bytes (entry 0: the background), read
+ *                  during the call; required iff channels == 3
+ * dyn, geom, geom_stride as cotix_render.  width: a multiple of 4 in
+ * [4, 1024]; height in [1, 1024]; image 4-byte aligned; B >= 1. */
+typedef struct cotix_camera {
+  float cx, cy, half_w, half_h; /* window centre and half extent (PyPainter's window: 0, 0, 8, 6) */
+  int follow_body;              /* -1: a fixed window; else the window moves with this body */
+  int follow_angle;             /* 1: ... and turns with it (needs follow_body >= 0) */
+} cotix_camera;
+int cotix_rasterize(const cotix_scene* scene, const float* dyn, const float* geom, int geom_stride, int B,
+                    const cotix_camera* cam, int width, int height, int channels, const unsigned char* palette,
+                    unsigned char* image, cotix_stream_t stream);
 
 /* Contract check (class_invariant, cotix/_design_by_contract.py:80-107, on the
  * world state): err[env] |= COTIX_ERR_STATE_NONFINITE when any dynamic state

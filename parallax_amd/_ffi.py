@@ -45,6 +45,11 @@ class CotixControl(ctypes.Structure):
                 ("saturate", _I), ("clip_lo", _F * 2), ("clip_hi", _F * 2)]
 
 
+class CotixCamera(ctypes.Structure):
+    """struct cotix_camera (include/cotix_amd.h)."""
+    _fields_ = [("cx", _F), ("cy", _F), ("half_w", _F), ("half_h", _F), ("follow_body", _I), ("follow_angle", _I)]
+
+
 SIGNATURES = {
     "cotix_params_default": (_I, [_P]),
     "cotix_scene_create": (_I, [_I, _P, _I, _P, _P, _P, ctypes.POINTER(_P)]),
@@ -97,6 +102,7 @@ SIGNATURES = {
     "cotix_observe": (_I, [_P, _I, _I, _P, _P]),
     "cotix_render_count": (_I, [_P]),
     "cotix_render": (_I, [_P, _P, _P, _I, _I, _P, _P]),
+    "cotix_rasterize": (_I, [_P, _P, _P, _I, _I, ctypes.POINTER(CotixCamera), _I, _I, _I, _P, _P, _P]),
     "cotix_check_state": (_I, [_P, _I, _I, _P, _P]),
     "cotix_last_error": (ctypes.c_char_p, []),
     "cotix_version": (ctypes.c_char_p, []),
@@ -105,7 +111,7 @@ SIGNATURES = {
 
 # entry points an older build given as COTIX_AMD_LIB (bench.py --lib, A/B
 # measurements against a parent commit) may lack; this tree's build has them
-OPTIONAL = {"cotix_scene_last_step_form", "cotix_eval_rollout", "cotix_eval_backward"}
+OPTIONAL = {"cotix_scene_last_step_form", "cotix_eval_rollout", "cotix_eval_backward", "cotix_rasterize"}
 
 
 def _load():

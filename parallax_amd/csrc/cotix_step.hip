@@ -17,6 +17,7 @@
 #include "cotix_body.h"
 #include "cotix_kernel.h"
 #include "cotix_launch.h"
+#include "cotix_raster.h"
 #include "cotix_scene.h"
 
 using cxk::FNS_ANALYTIC;
@@ -835,6 +836,63 @@ int cotix_render(const cotix_scene* scene, const float* dyn, const float* geom, 
   hipLaunchKernelGGL(render_kernel, dim3((unsigned)((n + 127) / 128)), dim3(128), 0,
                      reinterpret_cast<hipStream_t>(stream), dyn, B, geom, geom_stride, sp, nprim, prims);
   return hip_check(hipGetLastError(), "render_kernel launch");
+}
+
+// a group of lanes per env: the workgroup's four waves (the default), or one
+// wave with COTIX_RASTER_WAVE_PER_ENV=1 (A/B measurements; the same bits).
+// Read at every call: a test runs both forms in one process.
+static bool raster_wave_per_env() {
+  const char* v = getenv("COTIX_RASTER_WAVE_PER_ENV");
+  return v != nullptr && atoi(v) != 0;
+}
+
+int cotix_rasterize(const cotix_scene* scene, const float* dyn, const float* geom, int geom_stride, int B,
+                    const cotix_camera* cam, int width, int height, int channels, const unsigned char* palette,
+                    unsigned char* image, cotix_stream_t stream) {
+  if (!scene) return fail("null scene");
+  if (!dyn) return fail("null dyn");
+  if (!cam) return fail("null camera");
+  if (!image) return fail("null image");
+  if (B <= 0) return fail("rasterize: B must be positive");
+  if (width < 4 || width > 1024 || (width & 3) != 0) return fail("rasterize: width must be a multiple of 4 in [4, 1024]");
+  if (height < 1 || height > 1024) return fail("rasterize: height must be in [1, 1024]");
+  if (channels != 1 && channels != 3) return fail("rasterize: channels must be 1 (ids) or 3 (planar RGB)");
+  if (channels == 3 && !palette) return fail("rasterize: a palette is required for 3 channels");
+  if (channels == 1 && palette) return fail("rasterize: a palette needs 3 channels");
+  const SceneDev& s = scene->host;
+  if (cam->follow_body < -1 || cam->follow_body >= s.nb) return fail("rasterize: follow_body out of range");
+  if (cam->follow_angle != 0 && cam->follow_angle != 1) return fail("rasterize: follow_angle must be 0 or 1");
+  if (cam->follow_angle == 1 && cam->follow_body < 0) return fail("rasterize: follow_angle needs a followed body");
+  const auto finite = [](float x) { return x - x == 0.0f; };  // neither NaN nor infinite
+  if (!finite(cam->half_w) || !finite(cam->half_h) || !(cam->half_w > 0.0f) || !(cam->half_h > 0.0f))
+    return fail("rasterize: the camera's half extent must be finite and positive");
+  if (!finite(cam->cx) || !finite(cam->cy)) return fail("rasterize: the camera's centre must be finite");
+  if (!geom) return fail("rasterize: geometry required");
+  if (geom_stride != 0 && geom_stride < s.G) return fail("geom_stride smaller than the scene geometry");
+  if (s.nb > 255) return fail("rasterize: ids are bytes (at most 255 bodies)");
+  if ((reinterpret_cast<uintptr_t>(image) & 3u) != 0) return fail("rasterize: image must be 4-byte aligned");
+  cxk::SceneParts sp;
+  if (scene_parts(scene, &sp) < 0) return -1;
+  cxk::RasterParts rp{};
+  rp.np = sp.np;
+  for (int p = 0; p < sp.np; ++p) {
+    rp.body[p] = sp.body[p];
+    rp.kind[p] = sp.kind[p];
+    rp.nv[p] = sp.nv[p];
+    rp.goff[p] = sp.goff[p];
+    const unsigned char* c = palette ? palette + 3 * (sp.body[p] + 1) : nullptr;
+    rp.val[p] = c ? (uint32_t)c[0] | (uint32_t)c[1] << 8 | (uint32_t)c[2] << 16 : (uint32_t)(sp.body[p] + 1);
+  }
+  rp.bg = palette ? (uint32_t)palette[0] | (uint32_t)palette[1] << 8 | (uint32_t)palette[2] << 16 : 0u;
+  const cxk::RasterCam rc{cam->cx, cam->cy, cam->half_w, cam->half_h, cam->follow_body, cam->follow_angle};
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (raster_wave_per_env())
+    hipLaunchKernelGGL(cxk::raster_kernel<64>, dim3((unsigned)((B - 1) / 4 + 1)), dim3(cxk::RASTER_BLOCK), 0, st, dyn, B,
+                       geom, geom_stride, rp, rc, width, height, channels, image);
+  else
+    hipLaunchKernelGGL(cxk::raster_kernel<cxk::RASTER_BLOCK>, dim3((unsigned)B), dim3(cxk::RASTER_BLOCK), 0, st, dyn,
+                       B, geom, geom_stride, rp, rc, width, height, channels, image);
+  return hip_check(hipGetLastError(), "raster_kernel launch");
 }
 
 int cotix_observe(const float* dyn, int n_bodies, int B, float* obs, cotix_stream_t stream) {

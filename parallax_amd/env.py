@@ -140,6 +140,12 @@ class BatchedEnv:
         """The scenario's env.draw(painter) for env `env` (render export)."""
         return self.scenario.draw(painter, env)
 
+    def pixels(self, width, height, camera=None, rgb=False, out=None):
+        """Image observations of every env (render.pixels): uint8 [B, H, W]
+        body ids, or with rgb=True [B, 3, H, W] in the scenario's palette."""
+        from . import render as R
+        return R.pixels(self.world, width, height, camera, self.scenario.palette if rgb else None, out=out)
+
     @property
     def err(self):
         return self.world.err

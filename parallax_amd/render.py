@@ -11,6 +11,11 @@ get_edges order) and the static part -- which primitive, which colour, in
 which order -- is a command list built once per scenario.  replay() issues the
 reference's exact Painter call sequence for one env from that table, so any
 object with draw_circle / draw_line / next (a PyPainter included) works.
+
+pixels() goes the last step to an image observation: every env's filled
+bodies rasterized by one device kernel (cotix_rasterize, DESIGN.md section
+16) into a uint8 tensor of body ids or planar RGB -- filled bodies only: no
+outlines, none of LunarLander's two red lines, no anti-aliasing.
 """
 import torch
 
@@ -123,6 +128,79 @@ def replay(painter, cmds, prims, env=0):
         else:
             painter.draw_line(ref[0], ref[1], color)
     painter.next()
+
+
+class Camera:
+    """The window of pixels(): `center` +- `half_extent` in world units (the
+    default is PyPainter's 16 x 12 window around the origin), or, with
+    follow_body, in the frame of that body of every env: shifted by its
+    position and, with follow_angle, turned by its angle (an egocentric
+    view).  Immutable."""
+
+    __slots__ = ("center", "half_extent", "follow_body", "follow_angle")
+
+    def __init__(self, center=(0.0, 0.0), half_extent=(8.0, 6.0), follow_body=None, follow_angle=False):
+        set_ = object.__setattr__
+        set_(self, "center", (float(center[0]), float(center[1])))
+        set_(self, "half_extent", (float(half_extent[0]), float(half_extent[1])))
+        set_(self, "follow_body", None if follow_body is None else int(follow_body))
+        set_(self, "follow_angle", bool(follow_angle))
+
+    def __setattr__(self, name, value):
+        raise AttributeError("Camera is immutable: build a new one")
+
+    __delattr__ = __setattr__
+
+    def __repr__(self):
+        return "Camera(center=%r, half_extent=%r, follow_body=%r, follow_angle=%r)" % (
+            self.center, self.half_extent, self.follow_body, self.follow_angle)
+
+    def c_struct(self):
+        """struct cotix_camera (include/cotix_amd.h)."""
+        return _ffi.CotixCamera(self.center[0], self.center[1], self.half_extent[0], self.half_extent[1],
+                                -1 if self.follow_body is None else self.follow_body, 1 if self.follow_angle else 0)
+
+
+def palette_bytes(palette, n_bodies):
+    """A palette (n_bodies + 1 RGB triples, entry 0 the background) as the
+    3 * (n_bodies + 1) bytes cotix_rasterize reads."""
+    rows = [tuple(int(c) for c in rgb) for rgb in palette]
+    if len(rows) != n_bodies + 1 or any(len(r) != 3 or min(r) < 0 or max(r) > 255 for r in rows):
+        raise ValueError("palette must be %d RGB triples of bytes (the background, then one per body)"
+                         % (n_bodies + 1))
+    return bytes(c for r in rows for c in r)
+
+
+def pixels(world, width, height, camera=None, palette=None, dyn=None, out=None):
+    """Image observations of every env (cotix_rasterize): torch.uint8 on the
+    world's device, [B, H, W] body ids (0: background, 1 + b: body b, the
+    last body in scene order that covers the pixel) or, with a palette,
+    [B, 3, H, W] planar RGB.  camera: a Camera (default: PyPainter's window);
+    dyn: a state tensor in world.dyn's layout (default world.dyn); out: a
+    tensor of the result's shape to write into (no allocation per call)."""
+    width, height = int(width), int(height)
+    nb = len(world.bodies)
+    pal = None if palette is None else palette_bytes(palette, nb)
+    shape = (world.B, height, width) if pal is None else (world.B, 3, height, width)
+    d = world.dyn if dyn is None else dyn
+    if tuple(d.shape) != tuple(world.dyn.shape) or d.dtype != torch.float32 or d.device != world.dyn.device:
+        raise ValueError("dyn must be an f32 [n_bodies, 6, B] tensor on the world's device")
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=world.device)
+    elif tuple(out.shape) != shape or out.dtype != torch.uint8 or out.device != world.dyn.device \
+            or not out.is_contiguous():
+        raise ValueError("out must be a contiguous uint8 %s tensor on the world's device" % list(shape))
+    cam = (Camera() if camera is None else camera).c_struct()
+    _ffi.check(_ffi.lib.cotix_rasterize(world.scene.handle, _ffi.ptr(d), _ffi.ptr(world.geom), world.geom_stride,
+                                        world.B, cam, width, height, 1 if pal is None else 3, pal,
+                                        _ffi.ptr(out), _ffi.stream_ptr(world.device)), "cotix_rasterize")
+    return out
+
+
+def default_palette(bodies, background=(0, 0, 0)):
+    """The background, then DEFAULT_COLOR of each body's first part (what
+    shape.draw(painter) without a colour paints)."""
+    return [tuple(background)] + [DEFAULT_COLOR[_kind(b.shape.parts[0])] for b in bodies]
 
 
 class RecordingPainter:

@@ -121,6 +121,8 @@ class RoboCupEnv:
     # outline pass for the ball (cotix/_robocup.py:131-138)
     colors = [(0, 180, 0)] * 2 + [(255, 255, 0), (0, 128, 255), (255, 0, 0)]
     edge_colors = [(255, 255, 255)] * 2 + [(255, 255, 0), (0, 128, 255), None]
+    # pixels(): a black background, then the fill colour of every body
+    palette = [(0, 0, 0)] + colors
 
     def draw(self, painter, env=0, prims=None):
         """RoboCupEnv.draw(painter) (cotix/_robocup.py:140-150) for one env:
@@ -181,6 +183,12 @@ class BoxWorld:
             d[4] = 0.0
             d[5] = u[:, 4] * 10.0 - 5.0
         self.dyn_reset = self.world.dyn.clone()
+
+    @property
+    def palette(self):
+        """pixels(): black, then the default colour of each body's first part."""
+        from . import render as R
+        return R.default_palette(self.bodies)
 
 
 # ---------------------------------------------------------------------------
@@ -269,6 +277,12 @@ class LunarLander:
         self.dyn_reset = self.world.dyn.clone()
         # the polygon broadphase (results unchanged: the kernel certifies every pair it skips)
         self.stages = _ffi.STAGES_LUNAR | _ffi.STAGE_BROADPHASE
+
+    @property
+    def palette(self):
+        """pixels(): black, then the default colour of each body's first part."""
+        from . import render as R
+        return R.default_palette(self.bodies)
 
     def step(self):
         """LunarLander.step(): the joint constraints (cotix/_lunar_lander.py:145-218)."""
