@@ -34,6 +34,8 @@
  *                         cotix/_robocup.py:140-150, cotix/_lunar_lander.py:220-225
  *   cotix_rasterize       env.draw(painter) down to the pixel: u8 image observations
  *                         of every env (the filled bodies of cotix/_viz.py:55-75)
+ *   cotix_raycast         range-sensor observations: a fan of rays per env against the
+ *                         world parts, with edge_vs_edge  cotix/_contacts.py:206-225
  *   cotix_check_state     class_invariant  cotix/_design_by_contract.py:80-107
  *   cotix_eval            AbstractEnvironment.eval     cotix/_envs.py:37-132 with a
  *                         device AbstractJudge (:9-28) / AbstractControl
@@ -571,6 +573,52 @@ typedef struct cotix_camera {
 int cotix_rasterize(const cotix_scene* scene, const float* dyn, const float* geom, int geom_stride, int B,
                     const cotix_camera* cam, int width, int height, int channels, const unsigned char* palette,
                     unsigned char* image, cotix_stream_t stream);
+
+/* Range-sensor observations: n_rays rays cast from a sensor in every env, in
+ * one launch.  Every operation is one f32 operation
+ * rounded on its own; cross(u, v) = u.x*v.y - v.x*u.y, dot(u, v) = u.x*v.x +
+ * u.y*v.y.  For env g and ray k with the table's direction (x, y) = dirs[k]:
+ *   o = (ox, oy), d = (x, y)                                     body < 0
+ *   o = (ox, oy) + position of the body, d = (x, y)              follow_angle == 0
+ *   o = HomogenuousTransformer(position, angle).forward_vector((ox, oy)),
+ *   d = (c*x + (-s)*y, s*x + c*y), (c, s) its cos and sin        follow_angle == 1
+ * The world parts are those cotix_render exports, in scene order, without the
+ * parts of bodies named in ignore_mask.
+ *   AABB / polygon: the reference's edges (e0, e1) in the reference's order
+ *     (AABB: [up, (up.x, lo.y), lo, (lo.x, up.y)], edges (v_k, v_k+1); polygon:
+ *     edges (v_k, v_k-1)); s = e1 - e0, w = e0 - o, c = cross(d, s),
+ *     t = cross(w, s) / c, u = cross(w, d) / c: a crossing at distance t when
+ *     c != 0, 0 <= t <= max_range and 0 <= u <= 1 (edge_vs_edge, cotix/_contacts.py:206-225,
+ *     with the ray as the first edge and max_range in place of t <= 1)
+ *   circle (r, cen): m = o - cen, a = dot(d, d), b = dot(m, d), q = dot(m, m) - r*r,
+ *     sq = sqrt(b*b - a*q) (correctly rounded), t0 = (-b - sq) / a, t1 = (-b + sq) / a,
+ *     t = t0 >= 0 ? t0 : t1: a crossing when 0 <= t <= max_range
+ * dist[g][k] is the smallest such t -- over the parts in scene order and their
+ * edges in order, a crossing replaces the current one only when strictly
+ * nearer, so a tie keeps the earlier edge of the earlier part -- and hit[g][k]
+ * is 1 + that part's body; max_range and 0 where the ray crosses nothing.
+ * By design:
+ *   - these are boundary crossings, not entries: a ray that starts inside a
+ *     shape reports where it leaves it (mask such a body out to see past it);
+ *   - a NaN makes a comparison false: a NaN vertex removes only the edges that
+ *     touch it, a body with a NaN pose is invisible, and a sensor on a body with
+ *     a NaN pose reports max_range, 0 on every ray;
+ *   - a ray parallel to an edge (c == 0) does not cross it;
+ *   - directions are never renormalised: distances are in units of |d|;
+ *   - there is no culling of any kind.
+ * dirs device f32 [n_rays][2]; dist device f32 [B][n_rays]; hit device u8
+ * [B][n_rays] or NULL.  dyn, geom, geom_stride as cotix_rasterize.  B >= 1;
+ * n_rays in [1, 1024]. */
+typedef struct cotix_ray_sensor {
+  int body;             /* -1: fixed in the world; else mounted on this body */
+  int follow_angle;     /* 1: the fan turns with the body's angle (needs a body) */
+  float ox, oy;         /* the mount point, in the body's frame (the world's without a body) */
+  float max_range;      /* finite and positive */
+  uint32_t ignore_mask; /* bit b: body b's parts are invisible to the rays */
+} cotix_ray_sensor;
+int cotix_raycast(const cotix_scene* scene, const float* dyn, const float* geom, int geom_stride, int B,
+                  const cotix_ray_sensor* sensor, const float* dirs, int n_rays, float* dist, unsigned char* hit,
+                  cotix_stream_t stream);
 
 /* Contract check (class_invariant, cotix/_design_by_contract.py:80-107, on the
  * world state): err[env] |= COTIX_ERR_STATE_NONFINITE when any dynamic state

@@ -50,6 +50,12 @@ class CotixCamera(ctypes.Structure):
     _fields_ = [("cx", _F), ("cy", _F), ("half_w", _F), ("half_h", _F), ("follow_body", _I), ("follow_angle", _I)]
 
 
+class CotixRaySensor(ctypes.Structure):
+    """struct cotix_ray_sensor (include/cotix_amd.h)."""
+    _fields_ = [("body", _I), ("follow_angle", _I), ("ox", _F), ("oy", _F), ("max_range", _F),
+                ("ignore_mask", ctypes.c_uint32)]
+
+
 SIGNATURES = {
     "cotix_params_default": (_I, [_P]),
     "cotix_scene_create": (_I, [_I, _P, _I, _P, _P, _P, ctypes.POINTER(_P)]),
@@ -103,6 +109,7 @@ SIGNATURES = {
     "cotix_render_count": (_I, [_P]),
     "cotix_render": (_I, [_P, _P, _P, _I, _I, _P, _P]),
     "cotix_rasterize": (_I, [_P, _P, _P, _I, _I, ctypes.POINTER(CotixCamera), _I, _I, _I, _P, _P, _P]),
+    "cotix_raycast": (_I, [_P, _P, _P, _I, _I, ctypes.POINTER(CotixRaySensor), _P, _I, _P, _P, _P]),
     "cotix_check_state": (_I, [_P, _I, _I, _P, _P]),
     "cotix_last_error": (ctypes.c_char_p, []),
     "cotix_version": (ctypes.c_char_p, []),
@@ -111,7 +118,8 @@ SIGNATURES = {
 
 # entry points an older build given as COTIX_AMD_LIB (bench.py --lib, A/B
 # measurements against a parent commit) may lack; this tree's build has them
-OPTIONAL = {"cotix_scene_last_step_form", "cotix_eval_rollout", "cotix_eval_backward", "cotix_rasterize"}
+OPTIONAL = {"cotix_scene_last_step_form", "cotix_eval_rollout", "cotix_eval_backward", "cotix_rasterize",
+            "cotix_raycast"}
 
 
 def _load():

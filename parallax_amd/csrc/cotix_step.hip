@@ -18,6 +18,7 @@
 #include "cotix_kernel.h"
 #include "cotix_launch.h"
 #include "cotix_raster.h"
+#include "cotix_raycast.h"
 #include "cotix_scene.h"
 
 using cxk::FNS_ANALYTIC;
@@ -893,6 +894,45 @@ int cotix_rasterize(const cotix_scene* scene, const float* dyn, const float* geo
     hipLaunchKernelGGL(cxk::raster_kernel<cxk::RASTER_BLOCK>, dim3((unsigned)B), dim3(cxk::RASTER_BLOCK), 0, st, dyn,
                        B, geom, geom_stride, rp, rc, width, height, channels, image);
   return hip_check(hipGetLastError(), "raster_kernel launch");
+}
+
+int cotix_raycast(const cotix_scene* scene, const float* dyn, const float* geom, int geom_stride, int B,
+                  const cotix_ray_sensor* sensor, const float* dirs, int n_rays, float* dist, unsigned char* hit,
+                  cotix_stream_t stream) {
+  if (!scene) return fail("null scene");
+  if (!dyn) return fail("null dyn");
+  if (!sensor) return fail("null sensor");
+  if (!dirs) return fail("null dirs");
+  if (!dist) return fail("null dist");
+  if (B <= 0) return fail("raycast: B must be positive");
+  if (n_rays < 1 || n_rays > cxk::MAXRAYS) return fail("raycast: n_rays must be in [1, 1024]");
+  const SceneDev& s = scene->host;
+  if (sensor->body < -1 || sensor->body >= s.nb) return fail("raycast: body out of range");
+  if (sensor->follow_angle != 0 && sensor->follow_angle != 1) return fail("raycast: follow_angle must be 0 or 1");
+  if (sensor->follow_angle == 1 && sensor->body < 0) return fail("raycast: follow_angle needs a body");
+  const auto finite = [](float x) { return x - x == 0.0f; };  // neither NaN nor infinite
+  if (!finite(sensor->ox) || !finite(sensor->oy)) return fail("raycast: the sensor's offset must be finite");
+  if (!finite(sensor->max_range) || !(sensor->max_range > 0.0f))
+    return fail("raycast: max_range must be finite and positive");
+  if (s.nb < 32 && (sensor->ignore_mask >> s.nb) != 0u) return fail("raycast: ignore_mask names a body the scene lacks");
+  if (!geom) return fail("raycast: geometry required");
+  if (geom_stride != 0 && geom_stride < s.G) return fail("geom_stride smaller than the scene geometry");
+  cxk::SceneParts sp;
+  if (scene_parts(scene, &sp) < 0) return -1;
+  cxk::RasterParts rp{};  // the visible parts, in scene order; val: the id a crossing reports
+  for (int p = 0; p < sp.np; ++p) {
+    if (sp.body[p] < 32 && (sensor->ignore_mask >> sp.body[p] & 1u) != 0u) continue;
+    rp.body[rp.np] = sp.body[p];
+    rp.kind[rp.np] = sp.kind[p];
+    rp.nv[rp.np] = sp.nv[p];
+    rp.goff[rp.np] = sp.goff[p];
+    rp.val[rp.np] = (uint32_t)(sp.body[p] + 1);
+    ++rp.np;
+  }
+  const cxk::RaySensor rs{sensor->body, sensor->follow_angle, sensor->ox, sensor->oy, sensor->max_range};
+  hipLaunchKernelGGL(cxk::raycast_kernel, dim3((unsigned)((B - 1) / cxk::RAY_EPB + 1)), dim3(cxk::RAY_BLOCK), 0,
+                     reinterpret_cast<hipStream_t>(stream), dyn, B, geom, geom_stride, rp, rs, dirs, n_rays, dist, hit);
+  return hip_check(hipGetLastError(), "raycast_kernel launch");
 }
 
 int cotix_observe(const float* dyn, int n_bodies, int B, float* obs, cotix_stream_t stream) {

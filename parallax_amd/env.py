@@ -146,6 +146,12 @@ class BatchedEnv:
         from . import render as R
         return R.pixels(self.world, width, height, camera, self.scenario.palette if rgb else None, out=out)
 
+    def rays(self, sensor, dirs, out=None, hit_out=None):
+        """Range readings of every env (render.rays): (dist f32, hit uint8 or
+        None without hit_out), [B, n_rays] each."""
+        from . import render as R
+        return R.rays(self.world, sensor, dirs, out=out, hit_out=hit_out)
+
     @property
     def err(self):
         return self.world.err

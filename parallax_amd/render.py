@@ -16,7 +16,14 @@ pixels() goes the last step to an image observation: every env's filled
 bodies rasterized by one device kernel (cotix_rasterize, DESIGN.md section
 16) into a uint8 tensor of body ids or planar RGB -- filled bodies only: no
 outlines, none of LunarLander's two red lines, no anti-aliasing.
+
+rays() is the low-dimensional observation of the same geometry: a fan of rays
+cast from a RaySensor in every env by one device kernel (cotix_raycast,
+DESIGN.md section 17), each reporting the distance to the nearest boundary
+crossing of a part and that part's body.
 """
+import math
+
 import torch
 
 from . import _ffi
@@ -195,6 +202,96 @@ def pixels(world, width, height, camera=None, palette=None, dyn=None, out=None):
                                         world.B, cam, width, height, 1 if pal is None else 3, pal,
                                         _ffi.ptr(out), _ffi.stream_ptr(world.device)), "cotix_rasterize")
     return out
+
+
+class RaySensor:
+    """The range sensor of rays(): mounted at `offset` in the frame of `body`
+    of every env (shifted by its position and, with follow_angle, turned by
+    its angle), or, without a body, fixed at `offset` in the world.  Bodies in
+    `ignore` are invisible to the rays; by default that is the sensor's own
+    body, whose boundary every ray would otherwise cross on its way out.
+    Immutable."""
+
+    __slots__ = ("body", "offset", "follow_angle", "max_range", "ignore")
+
+    def __init__(self, body=None, offset=(0.0, 0.0), follow_angle=False, max_range=10.0, ignore=None):
+        set_ = object.__setattr__
+        set_(self, "body", None if body is None else int(body))
+        set_(self, "offset", (float(offset[0]), float(offset[1])))
+        set_(self, "follow_angle", bool(follow_angle))
+        set_(self, "max_range", float(max_range))
+        if ignore is None:
+            ignore = () if body is None else (body,)
+        ignore = tuple(sorted({int(b) for b in ignore}))
+        if any(b < 0 or b > 31 for b in ignore):
+            raise ValueError("ignore holds body indices in [0, 32)")
+        set_(self, "ignore", ignore)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("RaySensor is immutable: build a new one")
+
+    def __delattr__(self, name):
+        raise AttributeError("RaySensor is immutable: build a new one")
+
+    def __repr__(self):
+        return "RaySensor(body=%r, offset=%r, follow_angle=%r, max_range=%r, ignore=%r)" % (
+            self.body, self.offset, self.follow_angle, self.max_range, self.ignore)
+
+    @staticmethod
+    def fan(n, fov=2.0 * math.pi, start=None):
+        """The direction table of n rays spread evenly over `fov` radians:
+        ray k points at angle start + (k + 1/2) * fov / n, counter-clockwise
+        from the x axis of the sensor's frame; start defaults to -fov / 2, a
+        fan centred on that axis.  f32 [n, 2] on the host: cos and sin taken in
+        float64, then rounded."""
+        n = int(n)
+        if n < 1:
+            raise ValueError("a fan has at least one ray")
+        start = -0.5 * fov if start is None else float(start)
+        ang = start + (torch.arange(n, dtype=torch.float64) + 0.5) * (float(fov) / n)
+        return torch.stack([torch.cos(ang), torch.sin(ang)], dim=1).to(torch.float32)
+
+    def c_struct(self):
+        """struct cotix_ray_sensor (include/cotix_amd.h)."""
+        mask = 0
+        for b in self.ignore:
+            mask |= 1 << b
+        return _ffi.CotixRaySensor(-1 if self.body is None else self.body, 1 if self.follow_angle else 0,
+                                   self.offset[0], self.offset[1], self.max_range, mask)
+
+
+def rays(world, sensor, dirs, dyn=None, out=None, hit_out=None):
+    """Range readings of every env (cotix_raycast): (dist, hit), f32 and uint8
+    [B, n_rays] on the world's device.  dist is the distance, in units of the
+    direction's length, to the nearest boundary crossing of a visible part
+    along each ray, hit 1 + that part's body; sensor.max_range and 0 where
+    there is none.  These are crossings, not entries: a ray that starts inside
+    a shape reports where it leaves it.  dirs: f32 [n_rays, 2] on the world's
+    device (RaySensor.fan(n).to(device)); dyn: a state tensor in world.dyn's
+    layout (default world.dyn); out: a tensor of dist's shape to write into (no
+    allocation per call); hit_out: the tensor the ids are written into --
+    without one no ids are written and hit is None."""
+    dev = world.dyn.device
+    if not isinstance(sensor, RaySensor):
+        raise TypeError("sensor must be a RaySensor")
+    if not torch.is_tensor(dirs) or dirs.dim() != 2 or dirs.shape[1] != 2 or dirs.dtype != torch.float32 \
+            or dirs.device != dev or not dirs.is_contiguous():
+        raise ValueError("dirs must be a contiguous f32 [n_rays, 2] tensor on the world's device")
+    shape = (world.B, int(dirs.shape[0]))
+    d = world.dyn if dyn is None else dyn
+    if tuple(d.shape) != tuple(world.dyn.shape) or d.dtype != torch.float32 or d.device != dev:
+        raise ValueError("dyn must be an f32 [n_bodies, 6, B] tensor on the world's device")
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=dev)
+    elif tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != dev or not out.is_contiguous():
+        raise ValueError("out must be a contiguous f32 %s tensor on the world's device" % list(shape))
+    if hit_out is not None and (tuple(hit_out.shape) != shape or hit_out.dtype != torch.uint8 or hit_out.device != dev
+                                or not hit_out.is_contiguous()):
+        raise ValueError("hit_out must be a contiguous uint8 %s tensor on the world's device" % list(shape))
+    _ffi.check(_ffi.lib.cotix_raycast(world.scene.handle, _ffi.ptr(d), _ffi.ptr(world.geom), world.geom_stride,
+                                      world.B, sensor.c_struct(), _ffi.ptr(dirs), shape[1], _ffi.ptr(out),
+                                      _ffi.ptr(hit_out), _ffi.stream_ptr(world.device)), "cotix_raycast")
+    return out, hit_out
 
 
 def default_palette(bodies, background=(0, 0, 0)):
