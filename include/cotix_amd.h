@@ -620,6 +620,44 @@ int cotix_raycast(const cotix_scene* scene, const float* dyn, const float* geom,
                   const cotix_ray_sensor* sensor, const float* dirs, int n_rays, float* dist, unsigned char* hit,
                   cotix_stream_t stream);
 
+/* Range-sensor gradients: the vector-Jacobian product
+ * of cotix_raycast's dist with the cotangent g_dist (device f32 [B][n_rays]),
+ *   g_dyn  device f32 [n_bodies][6][B], dyn's layout: sum_k g_dist[g][k] *
+ *          d dist[g][k] / d (px, py, angle) of every body in rows 0, 1 and 4;
+ *          rows 2, 3 and 5 (the velocities) are 0, and so is the row of a body
+ *          no ray touched.  Every word is written.
+ *   g_geom device f32 [GW][B], GW = cotix_scene_geom_part_words, the layout of
+ *          cotix_rollout_backward_ex3's grad_geom: the same sum for every word
+ *          of env g's local geometry (a circle's pad word: 0).  Every word is
+ *          written.  With geom_stride == 0 column g is env g's derivative with
+ *          respect to the shared word (sum over g for a batch objective).
+ * Either output may be NULL, not both.  It needs no forward output: the rays
+ * are cast again.  The derivative is that of the executed branch:
+ *   - the winning crossing -- the part and its edge, or its circle root t0 /
+ *     t1 -- is held fixed, found by the forward's own comparisons and tie rule;
+ *   - order_clockwise's permutation is held fixed: the cotangent of a sorted
+ *     world vertex goes to the stored vertex it came from; nothing flows
+ *     through the sort keys, the mean or atan2;
+ *   - with (c, s) the body's cos and sin, d c = -s d angle, d s = c d angle;
+ *   - a ray that crosses nothing (hit == 0) contributes nothing, and so does a
+ *     ray whose g_dist is +-0: both are selects, so a NaN or inf cotangent on a
+ *     miss reaches no word; on any other ray a NaN g_dist reaches only the
+ *     words that ray touches;
+ *   - the sensor's body receives the cotangent of o and, with follow_angle,
+ *     that of d through its own frame; a body that is both the sensor's and
+ *     the one crossed gets both, the sensor's first;
+ *   - AABBs and circles do not turn with their body: their angle gradient is 0.
+ * Per ray the expressions are the plain derivatives of cotix_raycast's
+ * formulas for the winning feature, each one f32 operation
+ * (parallax_amd/csrc/cotix_raycast_grad.h lists them).  Each output word is the
+ * sum of its rays' addends in ascending ray index, starting from +0.0f: no
+ * atomics, the same bits on every run.  dirs, the sensor's offset and
+ * max_range are not differentiated.  Refuses what cotix_raycast refuses, a
+ * null g_dist and both outputs null, before any device call. */
+int cotix_raycast_backward(const cotix_scene* scene, const float* dyn, const float* geom, int geom_stride, int B,
+                           const cotix_ray_sensor* sensor, const float* dirs, int n_rays, const float* g_dist,
+                           float* g_dyn, float* g_geom, cotix_stream_t stream);
+
 /* Contract check (class_invariant, cotix/_design_by_contract.py:80-107, on the
  * world state): err[env] |= COTIX_ERR_STATE_NONFINITE when any dynamic state
  * word of the env is NaN or infinite.  err device u32 [B]. */

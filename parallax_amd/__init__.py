@@ -12,7 +12,7 @@ from .envs import (AbstractEnvironment, AffineControl, LinearJudge, PhysicsWorld
                    WorldState)
 from .eval_grad import differentiable_eval, eval_backward, eval_forward  # noqa: F401
 from .params import Params  # noqa: F401
-from .render import Camera, RaySensor  # noqa: F401
+from .render import Camera, RaySensor, differentiable_rays  # noqa: F401
 from .physics import (ContactInfo, ExplicitEulerPhysics, RandomizedCollider, SimpleConstraintSolver,  # noqa: F401
                       check_for_collision_convex, compute_penetration_vector_convex, contact_funcs,
                       resolve_collision, run_contacts)

@@ -110,6 +110,7 @@ SIGNATURES = {
     "cotix_render": (_I, [_P, _P, _P, _I, _I, _P, _P]),
     "cotix_rasterize": (_I, [_P, _P, _P, _I, _I, ctypes.POINTER(CotixCamera), _I, _I, _I, _P, _P, _P]),
     "cotix_raycast": (_I, [_P, _P, _P, _I, _I, ctypes.POINTER(CotixRaySensor), _P, _I, _P, _P, _P]),
+    "cotix_raycast_backward": (_I, [_P, _P, _P, _I, _I, ctypes.POINTER(CotixRaySensor), _P, _I, _P, _P, _P, _P]),
     "cotix_check_state": (_I, [_P, _I, _I, _P, _P]),
     "cotix_last_error": (ctypes.c_char_p, []),
     "cotix_version": (ctypes.c_char_p, []),
@@ -119,7 +120,7 @@ SIGNATURES = {
 # entry points an older build given as COTIX_AMD_LIB (bench.py --lib, A/B
 # measurements against a parent commit) may lack; this tree's build has them
 OPTIONAL = {"cotix_scene_last_step_form", "cotix_eval_rollout", "cotix_eval_backward", "cotix_rasterize",
-            "cotix_raycast"}
+            "cotix_raycast", "cotix_raycast_backward"}
 
 
 def _load():

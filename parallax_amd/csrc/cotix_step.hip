@@ -19,6 +19,7 @@
 #include "cotix_launch.h"
 #include "cotix_raster.h"
 #include "cotix_raycast.h"
+#include "cotix_raycast_grad.h"
 #include "cotix_scene.h"
 
 using cxk::FNS_ANALYTIC;
@@ -896,14 +897,17 @@ int cotix_rasterize(const cotix_scene* scene, const float* dyn, const float* geo
   return hip_check(hipGetLastError(), "raster_kernel launch");
 }
 
-int cotix_raycast(const cotix_scene* scene, const float* dyn, const float* geom, int geom_stride, int B,
-                  const cotix_ray_sensor* sensor, const float* dirs, int n_rays, float* dist, unsigned char* hit,
-                  cotix_stream_t stream) {
+// the argument checks of cotix_raycast and cotix_raycast_backward and the
+// visible parts; `refuse`: what is wrong with the entry's own pointers (checked
+// where the forward checks dist), or null
+static int raycast_setup(const cotix_scene* scene, const float* dyn, const float* geom, int geom_stride, int B,
+                         const cotix_ray_sensor* sensor, const float* dirs, int n_rays, const char* refuse,
+                         cxk::RasterParts* rp, cxk::RaySensor* rs) {
   if (!scene) return fail("null scene");
   if (!dyn) return fail("null dyn");
   if (!sensor) return fail("null sensor");
   if (!dirs) return fail("null dirs");
-  if (!dist) return fail("null dist");
+  if (refuse) return fail(refuse);
   if (B <= 0) return fail("raycast: B must be positive");
   if (n_rays < 1 || n_rays > cxk::MAXRAYS) return fail("raycast: n_rays must be in [1, 1024]");
   const SceneDev& s = scene->host;
@@ -919,20 +923,52 @@ int cotix_raycast(const cotix_scene* scene, const float* dyn, const float* geom,
   if (geom_stride != 0 && geom_stride < s.G) return fail("geom_stride smaller than the scene geometry");
   cxk::SceneParts sp;
   if (scene_parts(scene, &sp) < 0) return -1;
-  cxk::RasterParts rp{};  // the visible parts, in scene order; val: the id a crossing reports
+  *rp = cxk::RasterParts{};  // the visible parts, in scene order; val: the id a crossing reports
   for (int p = 0; p < sp.np; ++p) {
     if (sp.body[p] < 32 && (sensor->ignore_mask >> sp.body[p] & 1u) != 0u) continue;
-    rp.body[rp.np] = sp.body[p];
-    rp.kind[rp.np] = sp.kind[p];
-    rp.nv[rp.np] = sp.nv[p];
-    rp.goff[rp.np] = sp.goff[p];
-    rp.val[rp.np] = (uint32_t)(sp.body[p] + 1);
-    ++rp.np;
+    rp->body[rp->np] = sp.body[p];
+    rp->kind[rp->np] = sp.kind[p];
+    rp->nv[rp->np] = sp.nv[p];
+    rp->goff[rp->np] = sp.goff[p];
+    rp->val[rp->np] = (uint32_t)(sp.body[p] + 1);
+    ++rp->np;
   }
-  const cxk::RaySensor rs{sensor->body, sensor->follow_angle, sensor->ox, sensor->oy, sensor->max_range};
+  *rs = cxk::RaySensor{sensor->body, sensor->follow_angle, sensor->ox, sensor->oy, sensor->max_range};
+  return 0;
+}
+
+int cotix_raycast(const cotix_scene* scene, const float* dyn, const float* geom, int geom_stride, int B,
+                  const cotix_ray_sensor* sensor, const float* dirs, int n_rays, float* dist, unsigned char* hit,
+                  cotix_stream_t stream) {
+  cxk::RasterParts rp;
+  cxk::RaySensor rs;
+  if (raycast_setup(scene, dyn, geom, geom_stride, B, sensor, dirs, n_rays, dist ? nullptr : "null dist", &rp, &rs))
+    return -1;
   hipLaunchKernelGGL(cxk::raycast_kernel, dim3((unsigned)((B - 1) / cxk::RAY_EPB + 1)), dim3(cxk::RAY_BLOCK), 0,
                      reinterpret_cast<hipStream_t>(stream), dyn, B, geom, geom_stride, rp, rs, dirs, n_rays, dist, hit);
   return hip_check(hipGetLastError(), "raycast_kernel launch");
+}
+
+int cotix_raycast_backward(const cotix_scene* scene, const float* dyn, const float* geom, int geom_stride, int B,
+                           const cotix_ray_sensor* sensor, const float* dirs, int n_rays, const float* g_dist,
+                           float* g_dyn, float* g_geom, cotix_stream_t stream) {
+  cxk::RasterParts rp;
+  cxk::RaySensor rs;
+  const char* refuse = !g_dist ? "null g_dist" : ((!g_dyn && !g_geom) ? "raycast_backward: g_dyn and g_geom are both null"
+                                                                       : nullptr);
+  if (raycast_setup(scene, dyn, geom, geom_stride, B, sensor, dirs, n_rays, refuse, &rp, &rs)) return -1;
+  const int nb = scene->host.nb, gw = cxk::geom_part_words(scene->host);
+  if (nb > cxk::RG_MAXBODIES || gw < 0 || gw > cxk::RG_MAXGW)
+    return fail("raycast_backward: more than 16 bodies or 512 geometry words in the scene");
+  for (int p = 0; p < rp.np; ++p) {  // every word a record can name is an output word
+    const int nw = rp.kind[p] == cx::KIND_POLY ? 2 * rp.nv[p] : (rp.kind[p] == cx::KIND_AABB ? 4 : 3);
+    if (rp.goff[p] < 0 || rp.goff[p] + nw > gw || rp.nv[p] > cx::MAXV || rp.body[p] < 0 || rp.body[p] >= nb)
+      return fail("raycast_backward: a part's geometry words lie outside the scene's");
+  }
+  hipLaunchKernelGGL(cxk::raycast_grad_kernel, dim3((unsigned)((B - 1) / cxk::RG_EPB + 1)), dim3(cxk::RG_BLOCK), 0,
+                     reinterpret_cast<hipStream_t>(stream), dyn, B, geom, geom_stride, rp, rs, dirs, n_rays, g_dist, nb,
+                     gw, g_dyn, g_geom);
+  return hip_check(hipGetLastError(), "raycast_grad_kernel launch");
 }
 
 int cotix_observe(const float* dyn, int n_bodies, int B, float* obs, cotix_stream_t stream) {

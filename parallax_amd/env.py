@@ -152,6 +152,11 @@ class BatchedEnv:
         from . import render as R
         return R.rays(self.world, sensor, dirs, out=out, hit_out=hit_out)
 
+    def rays_backward(self, sensor, dirs, grad_dist, want_dyn=True, want_geom=False):
+        """The gradient of rays()' dist (render.rays_backward): (g_dyn, g_geom)."""
+        from . import render as R
+        return R.rays_backward(self.world, sensor, dirs, grad_dist, want_dyn=want_dyn, want_geom=want_geom)
+
     @property
     def err(self):
         return self.world.err

@@ -20,7 +20,10 @@ outlines, none of LunarLander's two red lines, no anti-aliasing.
 rays() is the low-dimensional observation of the same geometry: a fan of rays
 cast from a RaySensor in every env by one device kernel (cotix_raycast,
 DESIGN.md section 17), each reporting the distance to the nearest boundary
-crossing of a part and that part's body.
+crossing of a part and that part's body.  rays_backward() is its
+vector-Jacobian product with respect to every body's pose and every geometry
+word (cotix_raycast_backward) and differentiable_rays()
+the torch.autograd surface over the two.
 """
 import math
 
@@ -292,6 +295,107 @@ def rays(world, sensor, dirs, dyn=None, out=None, hit_out=None):
                                       world.B, sensor.c_struct(), _ffi.ptr(dirs), shape[1], _ffi.ptr(out),
                                       _ffi.ptr(hit_out), _ffi.stream_ptr(world.device)), "cotix_raycast")
     return out, hit_out
+
+
+def _check_dirs_dyn(world, sensor, dirs, dyn):
+    dev = world.dyn.device
+    if not isinstance(sensor, RaySensor):
+        raise TypeError("sensor must be a RaySensor")
+    if not torch.is_tensor(dirs) or dirs.dim() != 2 or dirs.shape[1] != 2 or dirs.dtype != torch.float32 \
+            or dirs.device != dev or not dirs.is_contiguous():
+        raise ValueError("dirs must be a contiguous f32 [n_rays, 2] tensor on the world's device")
+    d = world.dyn if dyn is None else dyn
+    if not torch.is_tensor(d) or tuple(d.shape) != tuple(world.dyn.shape) or d.dtype != torch.float32 \
+            or d.device != dev:
+        raise ValueError("dyn must be an f32 [n_bodies, 6, B] tensor on the world's device")
+    return d
+
+
+def rays_backward(world, sensor, dirs, grad_dist, dyn=None, want_dyn=True, want_geom=False):
+    """The vector-Jacobian product of rays()' dist with the cotangent
+    grad_dist (cotix_raycast_backward): (g_dyn, g_geom).
+    g_dyn, f32 [n_bodies, 6, B], holds sum_k grad_dist[env, k] * d dist[env, k]
+    / d (px, py, angle) of every body in rows 0, 1 and 4 (the velocity rows are
+    0); g_geom, f32 [GW, B], the same sum for every word of World.geometry() --
+    on shared geometry column `env` is that env's derivative with respect to
+    the shared word (sum over envs for a batch objective).  The one not wanted
+    is None.  The rays are cast again from `dyn` (default world.dyn) and the
+    world's geometry: the derivative is that of the crossing each ray reports,
+    held fixed; a ray that crosses nothing, and a ray whose grad_dist is 0,
+    contribute nothing whatever else grad_dist holds.  grad_dist: a contiguous
+    f32 [B, n_rays] tensor on the world's device."""
+    dev = world.dyn.device
+    d = _check_dirs_dyn(world, sensor, dirs, dyn)
+    shape = (world.B, int(dirs.shape[0]))
+    if not torch.is_tensor(grad_dist) or tuple(grad_dist.shape) != shape or grad_dist.dtype != torch.float32 \
+            or grad_dist.device != dev or not grad_dist.is_contiguous():
+        raise ValueError("grad_dist must be a contiguous f32 %s tensor on the world's device" % list(shape))
+    if not want_dyn and not want_geom:
+        raise ValueError("rays_backward: want_dyn and want_geom are both False")
+    gd = torch.empty(tuple(world.dyn.shape), dtype=torch.float32, device=dev) if want_dyn else None
+    gg = torch.empty(world.scene.geom_part_words, world.B, dtype=torch.float32, device=dev) if want_geom else None
+    _ffi.check(_ffi.lib.cotix_raycast_backward(
+        world.scene.handle, _ffi.ptr(d), _ffi.ptr(world.geom), world.geom_stride, world.B,
+        sensor.c_struct(), _ffi.ptr(dirs), shape[1], _ffi.ptr(grad_dist), _ffi.ptr(gd), _ffi.ptr(gg),
+        _ffi.stream_ptr(world.device)), "cotix_raycast_backward")
+    return gd, gg
+
+
+class _Rays(torch.autograd.Function):
+    """rays() with the state and, optionally, the geometry as differentiable inputs."""
+
+    @staticmethod
+    def forward(ctx, dyn, geometry, world, sensor, dirs, hit_out):
+        if geometry is not None:
+            world.geometry().copy_(geometry.detach())
+        # a private copy: a later step does not move what the rays were cast from
+        state = dyn.detach().clone(memory_format=torch.contiguous_format)
+        dist, _ = rays(world, sensor, dirs, dyn=state, hit_out=hit_out)
+        ctx.world, ctx.sensor, ctx.dirs, ctx.state = world, sensor, dirs, state
+        ctx.geom_version = world.geom._version
+        return dist
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_dist):
+        w = ctx.world
+        if w.geom._version != ctx.geom_version:
+            raise RuntimeError("the world's geometry changed between differentiable_rays() and backward()")
+        want_d, want_g = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not want_d and not want_g:
+            return None, None, None, None, None, None
+        gd, gg = rays_backward(w, ctx.sensor, ctx.dirs, g_dist.to(torch.float32).contiguous(), dyn=ctx.state,
+                               want_dyn=want_d, want_geom=want_g)
+        if want_g:
+            gg = gg.T.contiguous() if w.geom.dim() == 2 else gg.sum(dim=1)
+        return gd, gg, None, None, None, None
+
+
+def differentiable_rays(world, sensor, dirs, dyn=None, geometry=None, hit_out=None):
+    """rays()' dist, f32 [B, n_rays], differentiable through torch.autograd with
+    respect to `dyn` and `geometry` (the backward is cotix_raycast_backward:
+    rays_backward above states what the derivative is).
+
+    dyn: an f32 [n_bodies, 6, B] tensor on the world's device, which may
+    require grad (default: world.dyn, no gradient); its gradient has its shape,
+    with zeros in the velocity rows.  geometry: as rollout(geometry=): a float32
+    tensor of World.geometry()'s shape on the world's device, copied into
+    ``world.geom`` before the rays are cast; its gradient is [B, GW] on per-env
+    rows and the sum over the envs on shared geometry.  hit_out: as rays().
+
+    The forward keeps a copy of the state it cast from, so stepping the world
+    before backward() changes nothing; writing the world's geometry in between
+    raises RuntimeError.  dirs, the sensor's offset and max_range are not
+    differentiated, and the backward is not differentiable again."""
+    d = _check_dirs_dyn(world, sensor, dirs, dyn)
+    if geometry is not None:
+        have = world.geometry()
+        if not torch.is_tensor(geometry) or tuple(geometry.shape) != tuple(have.shape):
+            raise ValueError("geometry must be %s for this world, got %s" % (
+                tuple(have.shape), tuple(geometry.shape) if torch.is_tensor(geometry) else type(geometry)))
+        if geometry.dtype != torch.float32 or geometry.device != have.device:
+            raise ValueError("geometry must be a float32 tensor on the world's device")
+    return _Rays.apply(d, geometry, world, sensor, dirs, hit_out)
 
 
 def default_palette(bodies, background=(0, 0, 0)):
